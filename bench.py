@@ -11,14 +11,21 @@ frames from HBM. Steps alternate over two HIP streams (--streams, default 2; eac
 its own workspace and verdict buffer, one counters array): consecutive batches overlap, the next
 batch's ramp under the previous one's tail, as a NIC's queues would feed them.
 `roofline.kernel_avg_us` is then the device time per batch; `kernel_single_us` one launch at a
-time (measured after the timed region; `--streams 1` times that way throughout).
+time (measured after the timed region by `--full`; `--streams 1` times that way throughout).
+
+A plain run sets up, warms up, times the K steps and prints the line. `--full` adds, after the
+timed steps: the parity pins of the timed counters (`parity_pinned`), `kernel_single_us`, the
+PMC summary of the workload (`roofline.traffic`, `issue_roofline`) and the CPU baselines
+(`cpu_baseline`); a plain run leaves those fields null. `--dump-outputs DIR` writes what the last
+timed step returned (the verdict bytes of its batch, the counters of the timed steps) as
+DIR/<name>.npy; the batches are seeded, so two builds can be compared output for output.
 
 Multi-GPU (`bench.py --gpus N`, which starts N rank processes itself, or the same under
 python -m torch.distributed.run --nproc-per-node N): one rank per GPU, each rank owns its own
 shard of packets (weak scaling: per-GPU work fixed; pool batch k of rank r is seeded chunk
 k*N + r); the only collective is one RCCL all-reduce of the 8 per-verdict counters per job.
-value = packets of all ranks / max time. The reduced counters are checked against the oracle's
-counters of those chunks (tests/golden/bench_pins.json): `parity_pinned`.
+value = packets of all ranks / max time. With `--full` the reduced counters are checked against
+the oracle's counters of those chunks (tests/golden/bench_pins.json): `parity_pinned`.
 
 Prints ONE JSON line on rank 0.
 """
@@ -94,8 +101,18 @@ def parse():
                     help="ranks (one per GPU). Without WORLD_SIZE in the environment, N > 1 "
                          "starts N rank processes itself (before any GPU call); under torchrun "
                          "it must equal WORLD_SIZE. Default: WORLD_SIZE, else 1")
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also: the parity pins of the timed counters, one "
+                         "launch at a time (roofline.kernel_single_us), the PMC summary "
+                         "(roofline.traffic, issue_roofline) and the CPU baselines. A plain run "
+                         "times the steps and prints the line with those fields null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step's caller received as "
+                         "DIR/<name>.npy: verdict (float32, one per packet of the last batch; a "
+                         "seeded sample beyond 4 Mi packets) and counters (float64[8], the sums "
+                         "over the timed steps)")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="5tuple")
     ap.add_argument("--packets", type=int, default=1 << 20, help="packets per batch per GPU")
     ap.add_argument("--layout", choices=["fixed", "offsets", "pcap"], default="fixed",
@@ -131,7 +148,30 @@ def parse():
                     help="PMC summary (tools/pmc_summary.py output) of this workload: its HBM bytes"
                          " per launch (roofline.traffic) and VALU instructions (issue_roofline);"
                          " default profiles/pmc_<config>[_<slot>B].json")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX = 4 << 20  # --dump-outputs: verdicts written per rank (float32: 16 MiB)
+
+
+def dump_outputs(path, rank, verdict, cnt):
+    """--dump-outputs: the last timed step's verdict bytes (this rank's; beyond DUMP_MAX packets
+    a fixed seeded sample of them, in index order) as float32, and on rank 0 the counters of the
+    timed steps as float64 (exact: they stay below 2^53)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    if verdict.size > DUMP_MAX:
+        idx = np.sort(np.random.default_rng(0).choice(verdict.size, DUMP_MAX, replace=False))
+        verdict = verdict[idx]
+    np.save(os.path.join(path, "verdict.npy" if rank == 0 else f"verdict_rank{rank}.npy"),
+            verdict.astype(np.float32))
+    if rank == 0:
+        assert max(cnt) < 1 << 53, cnt
+        np.save(os.path.join(path, "counters.npy"), np.array(cnt, dtype=np.float64))
 
 
 def launch_ranks(n: int) -> int:
@@ -567,10 +607,12 @@ def main():
 
     cnt = [int(c) & ((1 << 64) - 1) for c in counters.cpu().tolist()]
     total_pkts = (args.total_packets or n * world) * args.steps
-    if not args.no_counters:
+    if args.dump_outputs:  # (before --full launches anything more into these buffers)
+        dump_outputs(args.dump_outputs, rank, verdicts[sof(K - 1, K)][:n].cpu().numpy(), cnt)
+    if args.full and not args.no_counters:
         assert sum(cnt[:7]) == total_pkts, (cnt, total_pkts)  # every packet: exactly one verdict
     pinned = None
-    if args.total_packets and args.config == "5tuple" and not args.no_counters:
+    if args.full and args.total_packets and args.config == "5tuple" and not args.no_counters:
         # parity of the benched workload: the global counters of the K steps equal K times the
         # oracle's counters of the same chunks (tests/golden/config4.json), checked after timing
         gp = os.path.join(ROOT, "tests", "golden", "config4.json")
@@ -583,7 +625,9 @@ def main():
                                      cnt, want)
                 pinned = "tests/golden/config4.json: counters == steps x fixture"
     pin_note = None
-    if args.long_options:
+    if not args.full:
+        pin_note = "not checked: the pins are part of --full"
+    elif args.long_options:
         pin_note = "frames modified by --long-options: no fixture"
     elif not args.total_packets and not args.no_counters:
         # parity of the timed weak-scaling work at any rank count: the global counters of the K
@@ -604,8 +648,8 @@ def main():
     wall_gbs = algo_bytes * args.steps / elapsed / 1e9
     # one launch at a time, after the timed region (not part of `value`): the kernel's own
     # duration, which rocprof's per-kernel average of a --streams 1 run reports
-    single_ms = kern_avg_ms
-    if S > 1:
+    single_ms = kern_avg_ms if S == 1 else None  # (S > 1: a run of its own, --full)
+    if S > 1 and args.full:
         c0 = torch.cuda.Event(enable_timing=True)
         c1 = torch.cuda.Event(enable_timing=True)
         kc = max(8, min(args.steps, 50))
@@ -625,7 +669,7 @@ def main():
               + ("_generic" if args.generic else ""))
     pj = args.pmc_json or os.path.join(ROOT, "profiles", f"pmc_{args.config}{suffix}.json")
     pmc_note = None
-    if os.path.exists(pj) and not args.total_packets and n == 1 << 20:
+    if args.full and os.path.exists(pj) and not args.total_packets and n == 1 << 20:
         with open(pj) as f:
             pmc = json.load(f)
         # a summary profiled on another build of the kernel does not describe this run: refuse
@@ -656,7 +700,7 @@ def main():
     if kid == _lib.EBPF_KERNEL_JIT_LOOP:  # (the loop program's kernel: plain or deep)
         kernel_name = prog.jit_loop_kernel() + " (compiled loop program)"
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline(args, img, batches[0], mixed, n, mem_size, r10)
 
     if issue is not None:
@@ -670,6 +714,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "settle_ms": args.settle_ms,
+            "full": args.full,
             "ms_per_step": round(elapsed * 1e3 / args.steps, 5),
             "higher_is_better": True,
             "scaling": "strong" if args.total_packets else "weak",
@@ -716,8 +761,10 @@ def main():
                 "streams": S,
                 # one launch at a time (S = 1: the timed region itself); rocprof's per-kernel
                 # average of a --streams 1 run
-                "kernel_single_us": round(single_ms * 1e3, 3),
-                "frac_single": round(algo_bytes / (single_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                # (null in a plain run with S > 1: measured by --full)
+                "kernel_single_us": round(single_ms * 1e3, 3) if single_ms else None,
+                "frac_single": (round(algo_bytes / (single_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
+                                if single_ms else None),
                 "kernel": kernel_name,
             },
             "issue_roofline": issue,

@@ -742,13 +742,15 @@ def test_concurrent_streams(cuda, config, own_ws):
 
 def test_bench_line(cuda):
     """bench.py's contract line (two streams, the default) on a small run: one JSON line with the
-    driver's keys, the roofline and its stream fields, and counters that add up to the packets."""
+    driver's keys, the roofline and its stream fields (--full: one launch at a time as well), and
+    counters that add up to the packets."""
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup",
-                        "2", "--cpu-seconds", "0", "--packets", str(1 << 16), "--pool-mib", "8"],
+                        "2", "--full", "--cpu-seconds", "0", "--packets", str(1 << 16),
+                        "--pool-mib", "8"],
                        capture_output=True, text=True, timeout=170, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -773,7 +775,8 @@ def test_bench_line(cuda):
 ])
 def test_bench_line_pinned(cuda, extra, env):
     """The default weak-scaling line at full batch size (1 Mi packets, the pool of 8 chunks per
-    rank) pins its timed counters to the oracle's fixture (tests/golden/bench_pins.json)."""
+    rank) with --full pins its timed counters to the oracle's fixture
+    (tests/golden/bench_pins.json)."""
     import subprocess
     import sys
 
@@ -781,7 +784,7 @@ def test_bench_line_pinned(cuda, extra, env):
     e = dict(os.environ, **env)
     e.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "11",
-                        "--warmup", "2", "--cpu-seconds", "0"] + extra,
+                        "--warmup", "2", "--full", "--cpu-seconds", "0"] + extra,
                        capture_output=True, text=True, timeout=170, cwd=root, env=e)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -792,6 +795,50 @@ def test_bench_line_pinned(cuda, extra, env):
     assert d["parity_pinned"] and f"k*{n}+r" in d["parity_pinned"], d.get("pin_note")
     c = d["counters"]
     assert c["drop"] + c["pass"] + c["other"] + c["faults"] == 11 * n * (1 << 20)
+
+
+def test_bench_plain_line_and_dump(cuda, oracle_mod, tmp_path):
+    """A plain run (no --full): the timed steps and the line only, the --full fields null; and
+    --dump-outputs writes the last step's verdicts (float32) and the timed steps' counters
+    (float64), which equal the oracle's over the same seeded batches."""
+    import subprocess
+    import sys
+
+    import bench
+    from ebpf_emu import workloads as W
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, steps = 1 << 16, 5
+    out = str(tmp_path / "dump")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps",
+                        str(steps), "--warmup", "2", "--packets", str(n), "--pool-mib", "8",
+                        "--dump-outputs", out],
+                       capture_output=True, text=True, timeout=170, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == steps and d["ms_per_step"] > 0 and d["full"] is False
+    assert d["cpu_baseline"] is None and d["parity_pinned"] is None
+    assert d["roofline"]["kernel_single_us"] is None and d["roofline"]["traffic"] is None
+    pool = d["config"]["pool_batches"]
+    assert pool == 2
+    assert sorted(os.listdir(out)) == ["counters.npy", "verdict.npy"]
+    verdict = np.load(os.path.join(out, "verdict.npy"))
+    counters = np.load(os.path.join(out, "counters.npy"))
+    assert verdict.dtype == np.float32 and verdict.shape == (n,)
+    assert counters.dtype == np.float64 and counters.shape == (8,)
+    op = oracle_mod.Program(W.program("5tuple"))
+    want = np.zeros(8, dtype=np.uint64)
+    for i in range(steps):
+        buf = W.frames_fixed(n, 64, bench.chunk_seed(bench.chunk_id(i % pool, 0, 1), False))
+        r0, st, cnt = op.run_batch(buf, n, stride=64, threads=4)
+        want += cnt
+    assert not st.any()
+    assert np.array_equal(verdict, np.where(r0 < 5, r0, 0xFE).astype(np.float32))
+    assert np.array_equal(counters, want.astype(np.float64))
 
 
 @pytest.mark.parametrize("slot,shift", [(64, 0), (80, 3), (80, 8), (81, 5)])

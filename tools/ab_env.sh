@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 2
 rounds="$1"; args="$2"; shift 2
 for r in $(seq "$rounds"); do
   for e in "$@"; do
-    line=$(env $e python bench.py --cpu-seconds 0 $args | tail -n 1) || exit $?
+    line=$(env $e python bench.py --full --cpu-seconds 0 $args | tail -n 1) || exit $?
     echo "$line" | python -c 'import json,sys; d=json.loads(sys.stdin.read()); r=d["roofline"]; print(sys.argv[1], "round", sys.argv[2], "value", d["value"], "event_us", r["kernel_avg_us"], "single_us", r["kernel_single_us"], "fixed_us", d["wall_fixed_us"])' "$e" "$r" || exit $?
   done
 done
