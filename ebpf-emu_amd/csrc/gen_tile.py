@@ -27,7 +27,7 @@ Only SALU/VALU/DS/SMEM, VGPR index mode and plain global loads/stores on VGPR ad
 readlane, DPP, trans, SDWA or VALU-written SGPRs feeding VMEM, so no gfx950 software wait states
 are needed inside (MI355X guide §5.7 item 2); M0 is saved on entry and restored on exit.
 
-  python3 gen_tile.py           # writes tile.inc and tile_ids.h next to this file
+  python3 gen_tile.py OUTDIR    # writes tile.inc, tile_ids.h and the JIT's files into OUTDIR
   python3 gen_tile.py --clobbers
 """
 import os
@@ -1940,7 +1940,23 @@ def handler_table():
     return out
 
 
-def main():
+def emit(outdir, name, desc, text, tag_after=None, c_code=False):
+    """Write one generated file: `text` is an asm statement with {NAME} register names, written
+    as C string literals (tag_after: the end of its marker line, which gets the JIT_STMT_TAG hook
+    that interp.hip defines around each #include), or, with c_code, C text written as it is."""
+    if not c_code:
+        text = F(text)
+        assert "{" not in text, "unsubstituted register name: " + text[text.index("{"):][:40]
+        text = cstr(text)
+    if tag_after:
+        assert text.count(tag_after + '\\n"') == 1
+        text = text.replace(tag_after + '\\n"', tag_after + '" JIT_STMT_TAG "\\n"')
+    with open(os.path.join(outdir, name), "w") as f:
+        f.write(f"// GENERATED by gen_tile.py -- do not edit. {desc}\n"
+                f"// clang-format off\n{text}\n// clang-format on\n")
+
+
+def main(outdir):
     table = handler_table()
     parts = [PROLOGUE + SLOTS_HEAD]
     for idx, (name, base, sfx) in enumerate(table):
@@ -1969,19 +1985,10 @@ def main():
         parts += [ldxk(sfx), ldxk1(sfx), ldxk2(sfx), ldxkfar(sfx), ldx(sfx), ldx_loop(sfx),
                   ldx1(sfx, False), ".if %[loops]", ldx1(sfx, True), ".endif", divmod(sfx)]
     parts += [KFAULT, ".if %[loops]", BUDGET, ".endif", EPILOGUE]
-    text = F("\n".join(parts))
-    assert "{" not in text, "unsubstituted register name: " + text[text.index("{"):][:40]
-    out = ["// GENERATED by gen_tile.py -- do not edit. One inline-asm statement (tile_kernel).",
-           "// clang-format off"]
-    for line in text.splitlines():
-        out.append('"' + line.replace("\\", "\\\\").replace('"', '\\"') + '\\n"')
-    out.append("// clang-format on")
-    with open(os.path.join(HERE, "tile.inc"), "w") as f:
-        f.write("\n".join(out) + "\n")
+    emit(outdir, "tile.inc", "One inline-asm statement (tile_kernel).", "\n".join(parts))
     # ids: T_<base>_C / T_<base>_E (byte offsets = id * TILE_SLOT)
-    ids = ["// GENERATED by gen_tile.py -- do not edit. Handler slots of tile.inc (uop.h TUop::hoff",
-           "// = id * TILE_SLOT). Chained (_C) forms continue with the next micro-op; block-end (_E)",
-           "// forms update the pc set and dispatch.",
+    ids = ["// Chained (_C) forms continue with the next micro-op; block-end (_E) forms update the pc",
+           "// set and dispatch.",
            "#pragma once", f"#define TILE_SLOT {SLOT}", f"#define TILE_NVGPR {NVGPR}"]
     for idx, (name, base, sfx) in enumerate(table):
         ids.append(f"#define T{name[1:]} {idx}")
@@ -1998,60 +2005,27 @@ def main():
     ids.append("// indexed by dag_asm.h H_* ids")
     ids.append("static const short kTileIdChained[] = {" + ", ".join(c_map) + "};")
     ids.append("static const short kTileIdEnd[] = {" + ", ".join(e_map) + "};")
-    with open(os.path.join(HERE, "tile_ids.h"), "w") as f:
-        f.write("\n".join(ids) + "\n")
-    # JIT: the template kernels' statements and the per-handler templates, indexed by tile id
-    text = F(JIT_STATEMENT)
-    assert "{" not in text
-    with open(os.path.join(HERE, "tile_jit.inc"), "w") as f:
-        f.write("// GENERATED by gen_tile.py -- do not edit. The JIT template kernel's statement.\n"
-                "// clang-format off\n" + cstr(text) + "\n// clang-format on\n")
-    # the var kernel's statement for stack-window programs (memory tier 0.5 on offsets / lens and
-    # xdp_md layouts: ebpf_tile_jit_var_stack, whose statement also owns v[64:95])
-    text = F(JIT_STATEMENT).replace("aligned=%[aligned]\n", "aligned=%[aligned] stack=1\n")
-    assert "stack=1" in text
-    with open(os.path.join(HERE, "tile_jit_stack.inc"), "w") as f:
-        f.write("// GENERATED by gen_tile.py -- do not edit. The JIT template kernel's statement for "
-                "stack-window programs.\n// clang-format off\n" + cstr(text) + "\n// clang-format on\n")
-    # the loop kernel's statement with a deeper refill prefetch (ebpf_tile_jit_loop_deep, whose
-    # statement also owns the prefetch stages v[72:103] and their tags v104, v105)
-    text = F(JIT_STATEMENT).replace("aligned=%[aligned]\n", "aligned=%[aligned] deep=1\n")
-    assert "deep=1" in text
-    with open(os.path.join(HERE, "tile_jit_deep.inc"), "w") as f:
-        f.write("// GENERATED by gen_tile.py -- do not edit. The JIT template kernel's statement for "
-                "loop programs with a deep refill prefetch.\n// clang-format off\n" + cstr(text) +
-                "\n// clang-format on\n")
+    emit(outdir, "tile_ids.h", "Handler slots of tile.inc (uop.h TUop::hoff = id * TILE_SLOT).",
+         "\n".join(ids), c_code=True)
+    # JIT: the template kernels' statements and the per-handler templates, indexed by tile id.
+    # interp.hip includes tile_jit.inc once per kernel flavour and names the flavour in the marker
+    # line through JIT_STMT_TAG: "" or " stack=1" (stack-window programs, whose statement also
+    # owns v[64:95]) or " deep=1" (the loop kernel with a deeper refill prefetch, which also owns
+    # the prefetch stages v[72:103] and their tags v104, v105)
+    emit(outdir, "tile_jit.inc", "The JIT template kernel's statement.", JIT_STATEMENT,
+         tag_after="aligned=%[aligned]")
     # the compiled fixed-slot kernel's tile loop (jit_statement_loop)
-    text = F(jit_statement_loop())
-    assert "{" not in text, "unsubstituted register name: " + text[text.index("{"):][:40]
-    with open(os.path.join(HERE, "tile_jit_loop.inc"), "w") as f:
-        f.write("// GENERATED by gen_tile.py -- do not edit. The compiled fixed-slot kernel's tile "
-                "loop (one statement, many tiles).\n// clang-format off\n" + cstr(text) +
-                "\n// clang-format on\n")
+    emit(outdir, "tile_jit_loop.inc",
+         "The compiled fixed-slot kernel's tile loop (one statement, many tiles).",
+         jit_statement_loop())
     # ... its occupancy variant (ebpf_tile_jit_fixed_occ: one window buffer per wave)
-    text = F(jit_statement_loop(single=True))
-    assert "{" not in text, "unsubstituted register name: " + text[text.index("{"):][:40]
-    with open(os.path.join(HERE, "tile_jit_loop1.inc"), "w") as f:
-        f.write("// GENERATED by gen_tile.py -- do not edit. The compiled fixed-slot kernel's tile "
-                "loop, one window buffer per wave (ebpf_tile_jit_fixed_occ).\n// clang-format off\n" +
-                cstr(text) + "\n// clang-format on\n")
-    # the compiled var kernel's tile loop (jit_statement_varl), and its statement for
+    emit(outdir, "tile_jit_loop1.inc", "The compiled fixed-slot kernel's tile loop, one window "
+         "buffer per wave (ebpf_tile_jit_fixed_occ).", jit_statement_loop(single=True))
+    # the compiled var kernel's tile loop (jit_statement_varl); JIT_STMT_TAG is " stack=1" for
     # stack-window programs (ebpf_tile_jit_varl_stack: the stack window in v[80:95] too)
-    text = F(jit_statement_varl())
-    assert "{" not in text, "unsubstituted register name: " + text[text.index("{"):][:40]
-    with open(os.path.join(HERE, "tile_jit_varl.inc"), "w") as f:
-        f.write("// GENERATED by gen_tile.py -- do not edit. The compiled var kernel's tile loop "
-                "(offsets + lens batches, one statement, many tiles).\n// clang-format off\n" +
-                cstr(text) + "\n// clang-format on\n")
-    text = text.replace(" varl=1\n", " varl=1 stack=1\n")
-    assert "stack=1" in text
-    with open(os.path.join(HERE, "tile_jit_varl_stack.inc"), "w") as f:
-        f.write("// GENERATED by gen_tile.py -- do not edit. The var tile loop's statement for "
-                "stack-window programs.\n// clang-format off\n" + cstr(text) +
-                "\n// clang-format on\n")
-    out = ["// GENERATED by gen_tile.py -- do not edit. Per-handler JIT templates (jit.cpp), indexed",
-           "// by tile id (tile_ids.h): {main text, out-of-line text}.", "#pragma once",
-           "// clang-format off", "static const char* const kJitTemplates[T_COUNT][2] = {"]
+    emit(outdir, "tile_jit_varl.inc", "The compiled var kernel's tile loop (offsets + lens "
+         "batches, one statement, many tiles).", jit_statement_varl(), tag_after=" varl=1")
+    out = ["#pragma once", "static const char* const kJitTemplates[T_COUNT][2] = {"]
     for idx, (name, base, sfx) in enumerate(table):
         main_t, ool_t = jit_template(base)
         out.append(f"// {name}\n{{{cstr(main_t)},\n{cstr(ool_t)}}},")
@@ -2070,16 +2044,17 @@ def main():
     out += ["static const char* const kJitInitReg[11] = {" + ",\n".join(inits) + "};"]
     # loop programs' window refill (refill() above): exec = the lanes whose access needs packet
     # bytes outside their window (T7), v36 = the address; WB = a & ~15 and 64 bytes from there
-    out += ["static const char* const kJitRefill =\n" + cstr(F(refill("x"))) + ";",
-            "// clang-format on"]
-    with open(os.path.join(HERE, "jit_tmpl.h"), "w") as f:
-        f.write("\n".join(out) + "\n")
+    out += ["static const char* const kJitRefill =\n" + cstr(F(refill("x"))) + ";"]
+    emit(outdir, "jit_tmpl.h", "Per-handler JIT templates (jit.cpp), indexed by tile id "
+         "(tile_ids.h): {main text, out-of-line text}.", "\n".join(out), c_code=True)
 
 
 if __name__ == "__main__":
     import sys
-    if len(sys.argv) > 1 and sys.argv[1] == "--clobbers":
+    if sys.argv[1:] == ["--clobbers"]:
         print(", ".join(f'"s{s}"' for s in SGPRS) + ", " +
               ", ".join(f'"v{v}"' for v in range(NVGPR)))
+    elif len(sys.argv) == 2:
+        main(sys.argv[1])
     else:
-        main()
+        sys.exit("usage: gen_tile.py OUTDIR | --clobbers")

@@ -1591,13 +1591,9 @@ constexpr uint32_t kVarlWaveLds = 2 * kWinBytes + 2 * kVarMetaBytes;
     "v95"
 // the deep-prefetch loop kernel (jit.cpp refill_prefetch, pf_depth > 1): prefetch stages 1 and 2
 // in v[72:87] and v[88:103], their window tags in v104, v105
-#define TILE_ASM_CLOBBER_DEEP "v72", "v73", "v74", "v75", "v76", "v77", "v78", "v79", "v80", "v81", \
-    "v82", "v83", "v84", "v85", "v86", "v87", "v88", "v89", "v90", "v91", "v92", "v93", "v94", \
-    "v95", "v96", "v97", "v98", "v99", "v100", "v101", "v102", "v103", "v104", "v105"
-#define TILE_ASM_CLOBBER_WINDOW "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71", "v72", \
-    "v73", "v74", "v75", "v76", "v77", "v78", "v79", "v80", "v81", "v82", "v83", "v84", "v85", \
-    "v86", "v87", "v88", "v89", "v90", "v91", "v92", "v93", "v94", "v95"
-
+#define TILE_ASM_CLOBBER_DEEP TILE_ASM_CLOBBER_WINDOW_HI, "v96", "v97", "v98", "v99", "v100", "v101", \
+    "v102", "v103", "v104", "v105"
+#define TILE_ASM_CLOBBER_WINDOW "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71", TILE_ASM_CLOBBER_WINDOW_HI
 
 // JIT: the statement of the compiled-program template kernels (tile_jit.inc; jit.cpp fills in the
 // program's code at load time). The compiled fixed-slot kernel (ebpf_tile_jit_fixed, below) has a
@@ -1605,9 +1601,10 @@ constexpr uint32_t kVarlWaveLds = 2 * kWinBytes + 2 * kVarMetaBytes;
 // next tile's DMA in flight while the current one runs).
 constexpr uint32_t kTileWaveLdsDb = 2 * kWinBytes;
 
-// STACK (with JIT, !FIXED, !LOOPS): the statement of stack-window programs, which also owns
-// v[64:95] (the preloaded header window and the stack window, jit.cpp body)
-// DEEP (with JIT, LOOPS): the loop statement whose refills prefetch two or three windows ahead
+// STACK (with JIT, !FIXED): the statement of stack-window programs, which also owns v[64:95] (the
+// preloaded header window and the stack window, jit.cpp body); DEEP (with JIT, LOOPS): the loop
+// statement whose refills prefetch two or three windows ahead. Both are tile_jit.inc under another
+// JIT_STMT_TAG (the end of the marker line that jit.cpp find_markers reads) and clobber list.
 template <bool FIXED, bool LOOPS, bool JIT, bool STACK = false, bool DEEP = false>
 __device__ __forceinline__ void tile_body(LaunchArgs& a) {
   constexpr uint32_t WPB = kWavesPerBlock;
@@ -1739,25 +1736,35 @@ __device__ __forceinline__ void tile_body(LaunchArgs& a) {
       }
     }
     if constexpr (JIT && LOOPS && STACK) {  // stack-window loop programs: v[56:95] too
+#define JIT_STMT_TAG " stack=1"
       asm volatile(
-#include "tile_jit_stack.inc"
+#include "tile_jit.inc"
           TILE_ASM_OPERANDS, TILE_ASM_CLOBBER_PREFETCH, TILE_ASM_CLOBBER_WINDOW_HI);
+#undef JIT_STMT_TAG
     } else if constexpr (JIT && LOOPS && DEEP) {  // + the deeper prefetch's stages
+#define JIT_STMT_TAG " deep=1"
       asm volatile(
-#include "tile_jit_deep.inc"
+#include "tile_jit.inc"
           TILE_ASM_OPERANDS, TILE_ASM_CLOBBER_PREFETCH, TILE_ASM_CLOBBER_DEEP);
+#undef JIT_STMT_TAG
     } else if constexpr (JIT && LOOPS) {  // + the refill prefetch registers of compiled loop programs
+#define JIT_STMT_TAG ""
       asm volatile(
 #include "tile_jit.inc"
           TILE_ASM_OPERANDS, TILE_ASM_CLOBBER_PREFETCH);
+#undef JIT_STMT_TAG
     } else if constexpr (JIT && STACK) {
+#define JIT_STMT_TAG " stack=1"
       asm volatile(
-#include "tile_jit_stack.inc"
+#include "tile_jit.inc"
           TILE_ASM_OPERANDS, TILE_ASM_CLOBBER_WINDOW);
+#undef JIT_STMT_TAG
     } else if constexpr (JIT) {
+#define JIT_STMT_TAG ""
       asm volatile(
 #include "tile_jit.inc"
           TILE_ASM_OPERANDS);
+#undef JIT_STMT_TAG
     } else {
       asm volatile(
 #include "tile.inc"
@@ -2122,13 +2129,17 @@ __device__ __forceinline__ void varl_body(LaunchArgs& a) {
     uint32_t ret = 0, cdn, stg;
     uint64_t dmask;  // (store mode: the lanes whose overflow image is live, per tile)
     if constexpr (STACK) {
-      asm volatile(
-#include "tile_jit_varl_stack.inc"
-          VARL_OPERANDS);
-    } else {
+#define JIT_STMT_TAG " stack=1"
       asm volatile(
 #include "tile_jit_varl.inc"
           VARL_OPERANDS);
+#undef JIT_STMT_TAG
+    } else {
+#define JIT_STMT_TAG ""
+      asm volatile(
+#include "tile_jit_varl.inc"
+          VARL_OPERANDS);
+#undef JIT_STMT_TAG
     }
     // (scalar loop state back through readfirstlane: the statement has VGPR outputs)
     tile = rfl(tile);

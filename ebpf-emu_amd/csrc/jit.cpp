@@ -177,18 +177,30 @@ void replace_token(std::string& s, const std::string& from, const std::string& t
   }
 }
 
+// The lines of a text (a last line need not end in '\n'), and lines back into text, each ended.
+std::vector<std::string> split_lines(const std::string& text) {
+  std::vector<std::string> lines;
+  for (size_t p = 0; p < text.size();) {
+    size_t e = text.find('\n', p);
+    if (e == std::string::npos) e = text.size();
+    lines.push_back(text.substr(p, e - p));
+    p = e + 1;
+  }
+  return lines;
+}
+std::string join_lines(const std::vector<std::string>& lines) {
+  std::string out;
+  for (const std::string& l : lines) out += l + "\n";
+  return out;
+}
+
 // Resolve the assembler conditionals of an expanded handler (".if 1", ".if 0 == 0", ...; the
 // statement's %[fixed] / %[loops] are known here), so only the live branch is emitted (and the
 // peepholes see straight-line code). Text with any other condition is returned unchanged.
 std::string resolve_ifs(const std::string& text) {
   std::string out;
   std::vector<std::pair<bool, bool>> st;  // (this branch active, enclosing active)
-  size_t p = 0;
-  while (p < text.size()) {
-    size_t e = text.find('\n', p);
-    if (e == std::string::npos) e = text.size();
-    const std::string ln = text.substr(p, e - p);
-    p = e + 1;
+  for (const std::string& ln : split_lines(text)) {
     const bool live = st.empty() || (st.back().first && st.back().second);
     if (ln.compare(0, 4, ".if ") == 0) {
       long a = 0, b = 0;
@@ -219,14 +231,7 @@ std::string resolve_ifs(const std::string& text) {
 }
 
 std::string fold_copy(const std::string& text, uint32_t tmp) {
-  std::vector<std::string> lines;
-  size_t p = 0;
-  while (p < text.size()) {
-    size_t e = text.find('\n', p);
-    if (e == std::string::npos) e = text.size();
-    lines.push_back(text.substr(p, e - p));
-    p = e + 1;
-  }
+  const std::vector<std::string> lines = split_lines(text);
   const std::string tpair = "v[" + std::to_string(tmp) + ":" + std::to_string(tmp + 1) + "]";
   const std::string head = "v_mov_b64 " + tpair + ", ";
   size_t l0 = lines.size();
@@ -3541,13 +3546,7 @@ struct Compiler {
   // xor with an operand that is not the destination (`mov r8, r5; and r8, 0xff`, a rule's mask):
   // the two halves' ops from the moved source (an and with 0 a move of 0).
   static std::string peephole(const std::string& text) {
-    std::vector<std::string> ln;
-    for (size_t p = 0; p < text.size();) {
-      size_t e = text.find('\n', p);
-      if (e == std::string::npos) e = text.size();
-      ln.push_back(text.substr(p, e - p));
-      p = e + 1;
-    }
+    std::vector<std::string> ln = split_lines(text);
     std::string out;
     for (size_t i = 0; i < ln.size(); i++) {
       uint32_t d0, d1, s0, s1;
@@ -3606,13 +3605,7 @@ struct Compiler {
   // OR-ed into the mask, exec &= vcc) after a VOPC compare into vcc: the compare negated, so the
   // leaving lanes are vcc and the mask takes them directly (two SALU instead of three).
   static std::string negate_leave(const std::string& text) {
-    std::vector<std::string> ln;
-    for (size_t p = 0; p < text.size();) {
-      size_t e = text.find('\n', p);
-      if (e == std::string::npos) e = text.size();
-      ln.push_back(text.substr(p, e - p));
-      p = e + 1;
-    }
+    std::vector<std::string> ln = split_lines(text);
     static const std::map<std::string, std::string> neg = {
         {"eq", "ne"}, {"ne", "eq"}, {"gt", "le"}, {"le", "gt"}, {"ge", "lt"}, {"lt", "ge"}};
     std::vector<std::string> out;
@@ -3637,9 +3630,7 @@ struct Compiler {
       }
       out.push_back(ln[i]);
     }
-    std::string r;
-    for (const std::string& l : out) r += l + "\n";
-    return r;
+    return join_lines(out);
   }
 
   // A compare into vcc whose only use is the exec update right after it (comments between):
@@ -3647,13 +3638,7 @@ struct Compiler {
   // `s_andn2_b64 exec, exec, vcc` the negated compare -- the tests of a complement region
   // (cm_assign), one VALU instruction each.
   static std::string cmpx_pass(const std::string& text) {
-    std::vector<std::string> ln;
-    for (size_t p = 0; p < text.size();) {
-      size_t e = text.find('\n', p);
-      if (e == std::string::npos) e = text.size();
-      ln.push_back(text.substr(p, e - p));
-      p = e + 1;
-    }
+    std::vector<std::string> ln = split_lines(text);
     static const std::map<std::string, std::string> neg = {
         {"eq", "ne"}, {"ne", "eq"}, {"gt", "le"}, {"le", "gt"}, {"ge", "lt"}, {"lt", "ge"}};
     std::vector<std::string> out;
@@ -3674,19 +3659,11 @@ struct Compiler {
       if (ln[i] == "; cmx") continue;
       out.push_back(ln[i]);
     }
-    std::string r;
-    for (const std::string& l : out) r += l + "\n";
-    return r;
+    return join_lines(out);
   }
 
   static std::string sink_high_zero(const std::string& text) {
-    std::vector<std::string> ln;
-    for (size_t p = 0; p < text.size();) {
-      size_t e = text.find('\n', p);
-      if (e == std::string::npos) e = text.size();
-      ln.push_back(text.substr(p, e - p));
-      p = e + 1;
-    }
+    std::vector<std::string> ln = split_lines(text);
     auto names = [](const std::string& l, const std::string& v) {
       for (size_t q = 0; (q = l.find(v, q)) != std::string::npos; q += v.size()) {
         const bool lo = q == 0 || !(isalnum((unsigned char)l[q - 1]) || l[q - 1] == '_');
@@ -3778,9 +3755,7 @@ struct Compiler {
         ins--;
       }
     }
-    std::string r;
-    for (const std::string& l : ln) r += l + "\n";
-    return r;
+    return join_lines(ln);
   }
 
   // A 64-bit compare of a register whose high half was just zeroed with a constant below 2^32
@@ -3790,13 +3765,7 @@ struct Compiler {
   // unsigned compare of the low halves gives the same vcc -- with K as the VOPC's literal (the
   // s_movs of s[48:49] go: a micro-op's code sets every field register it reads).
   static std::string narrow_compares(const std::string& text) {
-    std::vector<std::string> ln;
-    for (size_t p = 0; p < text.size();) {
-      size_t e = text.find('\n', p);
-      if (e == std::string::npos) e = text.size();
-      ln.push_back(text.substr(p, e - p));
-      p = e + 1;
-    }
+    std::vector<std::string> ln = split_lines(text);
     std::vector<std::string> out;
     for (size_t i = 0; i < ln.size(); i++) {
       char op[8], sg;
@@ -3833,9 +3802,7 @@ struct Compiler {
       }
       out.push_back(ln[i]);
     }
-    std::string r;
-    for (const std::string& l : out) r += l + "\n";
-    return r;
+    return join_lines(out);
   }
 };
 
