@@ -233,10 +233,11 @@ JUNK_REGS = [0x0123456789ABCDEF, 0, 0xFFFFFFFF00000010, 0x8000000000000003, 0x7F
              0x1111111122222222, 0x3333333344444444, 0xFFFFFFFFFFFFFFFF, 0x80000000, 0x5555555566666666]
 
 
-def oracle_ref(oracle_mod, img: bytes, pkts, init_regs=None):
+def oracle_ref(oracle_mod, img: bytes, pkts, init_regs=None, mem_size=1024, r10=512):
     """oracle.Program.run_full over the batch, once: statuses, registers, verdict bytes and the 8
     counters (test_gpu_jit._vs_oracle's rule: r0 < 5 its own bucket, else bucket 5; faults bucket 6;
-    retired steps bucket 7)."""
+    retired steps bucket 7). pkts: what the oracle runs on (an xdp_md batch's ctx-prefixed
+    images)."""
     import numpy as np
 
     op = oracle_mod.Program(img)
@@ -247,7 +248,7 @@ def oracle_ref(oracle_mod, img: bytes, pkts, init_regs=None):
     cnt = np.zeros(8, dtype=np.uint64)
     for i, p in enumerate(pkts):
         kw = {} if init_regs is None else dict(init_regs=list(init_regs))
-        s, r, _mem, steps = op.run_full(p, 1024, 512, STEPS, **kw)
+        s, r, _mem, steps = op.run_full(p, mem_size, r10, STEPS, **kw)
         st[i] = s
         regs[i] = r
         if s == 0:
@@ -297,16 +298,21 @@ def launch(prog, frames, kw, want_kernels, prod=False, **flags):
     return out
 
 
-def mismatch(p: Prog, route: str, img: bytes, prs, got, ref, full=None):
+def mismatch(p, route: str, img: bytes, prs, got, ref, full=None, lane_text=None):
     """None, or the first difference as one line that reproduces it: the program's operator,
     class and operand form, the route, the lane's (a, b) and the image. `got` against the oracle's
-    `ref`; a production launch (no registers) also against the full launch of the same batch."""
+    `ref`; a production launch (no registers) also against the full launch of the same batch.
+    lane_text(i): another matrix's description of lane i (loadmatrix.py), in place of (a, b)."""
     import numpy as np
 
     def lane(i, what, g, w):
-        a, b = prs[i]
+        if lane_text is not None:
+            where = lane_text(i)
+        else:
+            a, b = prs[i]
+            where = f"(a, b) = ({a:#x}, {b:#x})"
         return (f"{p.what} [{p.name}] route {route}: {what} got {g} want {w} at lane {i} "
-                f"(a, b) = ({a:#x}, {b:#x}) image {img.hex()}")
+                f"{where} image {img.hex()}")
 
     ok = ref["status"] == 0
     for key in ("status", "verdict"):
