@@ -277,7 +277,19 @@ struct ebpf_prog {
   bool pjit_deep = false;  // variant 4 compiled into ebpf_tile_jit_loop_deep
   bool xjit_deep = false;  // variant 5 likewise
   bool rjit_deep = false;  // variant 6 likewise
+  // the write-back variant (EBPF_BATCH_WRITEBACK; ebpf_prog_jit_asm's variant 7): variant 1's
+  // program of a stack-window program with packet stores, its code followed by the stores of the
+  // rewritten packet bytes (jit.cpp wb_store_mode / wb_const). Compiled on the first use of the
+  // flag (wb_compile_locked), so the other variants and a flag-off process pay nothing.
+  // wb_state: 0 not compiled yet, 1 compiled, 2 failed or not such a program
+  int wb_state = 0;
+  std::string wb_err;  // why it failed (ebpf_prog_jit_error appends it)
+  std::vector<char> wb_co;
+  std::string wb_asm;
+  hipModule_t wb_mod[kMaxDevices] = {};
+  JitFns wb_fn[kMaxDevices];
 };
+constexpr int kJitVariantWb = kJitVariants;  // ebpf_prog_jit_asm's id of the write-back variant
 
 // Diagnostics: EBPFEMU_TRACE=1 gives the compiled fixed-slot kernel a per-device stamp buffer
 // (LaunchArgs::trace, kTraceWaves x kTraceSlots u64), zeroed before each launch;
@@ -470,6 +482,48 @@ static int jit_compile_locked(ebpf_prog* p) {
     }
   }
   return p->jit_state == 1 ? 1 : p->jit_state == 2 ? 0 : p->jit_state;
+}
+
+// Whether the program's compiled stack kernels hold stores a write-back batch must store back to
+// the packets (the write-back variant's code).
+// (every stack-window program: a packet that reaches into the window [r10 - k, r10) has the
+// window's stores among its bytes)
+static bool wb_needed(const ebpf_prog* p) { return p->stack.k != 0; }
+
+// Compile the write-back variant (caller holds p->mu). True when it exists.
+static bool wb_compile_locked(ebpf_prog* p) {
+  if (p->wb_state == 0) {
+    p->wb_state = 2;
+    if (jit_compile_locked(p) == 1 && wb_needed(p) && p->jit_has[1] && !p->tuopsk.empty()) {
+      std::string err;
+      if (jit_compile(p->xuops, p->tuopsk, p->wb_co, &err, &p->wb_asm, &p->stack, nullptr, true,
+                      true)) {
+        p->wb_state = 1;
+      } else {
+        p->wb_co.clear();
+        p->wb_err = "write-back variant: " + (err.empty() ? std::string("the compiler failed") : err);
+      }
+    }
+  }
+  return p->wb_state == 1;
+}
+
+// ... and load it on `device` (current). A failure leaves the general interpreter's write-back.
+static void wb_upload(ebpf_prog* p, int device) {
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->wb_mod[device] || !wb_compile_locked(p)) return;
+  int cur = device_of_current();
+  if (cur != device) hipSetDevice(device);
+  if (jit_load(p->wb_co, &p->wb_mod[device], &p->wb_fn[device])) {
+    p->wb_fn[device].var_only = false;
+    p->wb_fn[device].fixed_occ = p->wb_fn[device].fixed_occw = nullptr;
+  } else {  // (recorded once: later write-back batches run the general interpreter, no reload)
+    p->wb_mod[device] = nullptr;
+    p->wb_state = 2;
+    p->wb_co.clear();
+    p->wb_err = "write-back variant: the code object did not load";
+  }
+  if (cur != device) hipSetDevice(cur);
 }
 
 // Length-binned lane packing for the loop-mode tile kernel (EBPFEMU_BIN=0|1 forces it off/on;
@@ -1463,6 +1517,10 @@ void ebpf_prog_free(ebpf_prog* p) {
         hipSetDevice(d);
         (void)hipModuleUnload(p->jit_mod[d][v]);
       }
+    if (p->wb_mod[d]) {
+      hipSetDevice(d);
+      (void)hipModuleUnload(p->wb_mod[d]);
+    }
   }
   hipSetDevice(cur);
   delete p;
@@ -1512,10 +1570,12 @@ int ebpf_prog_compile(ebpf_prog* p) {
 }
 
 int ebpf_prog_jit_asm(ebpf_prog* p, int variant, char* buf, size_t cap, size_t* len) {
-  if (!p || variant < 0 || variant >= kJitVariants) return EBPF_EINVAL;
+  if (!p || variant < 0 || variant > kJitVariantWb) return EBPF_EINVAL;
   std::lock_guard<std::mutex> lk(p->mu);
-  if (jit_compile_locked(p) != 1 || !p->jit_has[variant]) return EBPF_EINVAL;
-  const std::string& a = p->jit_asm[variant];
+  if (variant == kJitVariantWb ? !wb_compile_locked(p)
+                               : jit_compile_locked(p) != 1 || !p->jit_has[variant])
+    return EBPF_EINVAL;
+  const std::string& a = variant == kJitVariantWb ? p->wb_asm : p->jit_asm[variant];
   if (len) *len = a.size();
   if (buf && cap) {
     const size_t k = std::min(cap - 1, a.size());
@@ -1543,6 +1603,9 @@ int ebpf_prog_jit_error(ebpf_prog* p, char* buf, size_t cap, size_t* len) {
     else
       m = "not compiled";
   }
+  // (the write-back variant, once a batch or ebpf_prog_jit_asm has asked for it: its batches run
+  // the general interpreter's write-back when it failed)
+  if (!p->wb_err.empty()) m += (m.empty() ? "" : "; ") + p->wb_err;
   if (len) *len = m.size();
   if (buf && cap) {
     const size_t k = std::min(cap - 1, m.size());
@@ -1689,7 +1752,10 @@ static bool stack_var_ok(const ebpf_prog* p, const ebpf_batch* b) {
 // past every packet byte, so it starts as zeros; other layouts: stack_var_ok).
 static bool stack_launch_ok(const ebpf_prog* p, const ebpf_batch* b, const ebpf_batch_out* out,
                             int device) {
-  if (!stack_common_ok(p, b, out) || !p->jit_mod[device][1] || b->max_steps < p->xuops.size())
+  // (a write-back batch of a program with packet stores: the write-back variant's code)
+  const bool wbv = (b->flags & EBPF_BATCH_WRITEBACK) && wb_needed(p);
+  if (!stack_common_ok(p, b, out) || !(wbv ? p->wb_mod[device] : p->jit_mod[device][1]) ||
+      b->max_steps < p->xuops.size())
     return false;
   const uint64_t k = p->stack.k, r10 = b->r10;
   LaunchArgs la{};
@@ -1704,6 +1770,13 @@ static bool stack_launch_ok(const ebpf_prog* p, const ebpf_batch* b, const ebpf_
   const uint64_t img_len = b->stride + ((b->flags & EBPF_BATCH_XDP_MD) ? 8 : 0);
   if (fixed ? r10 - k < img_len : !stack_var_ok(p, b)) return false;
   if (p->stack.any_dyn && b->mem_size < (uint64_t)kWin) return false;
+  if (wbv) {  // the write-back code is in the two tile loops' statements: the per-tile var kernel's
+              // batches (unaligned metadata, ...) write back on the general interpreter
+    la.n_uops = (uint32_t)p->xuops.size();
+    la.n_tiles = (b->n + 63) / 64;
+    const int id = launch_kernel_id(kKindDag, la, &p->wb_fn[device], true);
+    if (id != EBPF_KERNEL_JIT_STACK && id != EBPF_KERNEL_JIT_VARL_STACK) return false;
+  }
   for (const auto& kl : p->kloads) {
     if (kl.first < r10 && kl.first + kl.second > r10 - k) return false;
     // packet-window stores: the compiled code has only the copy whose window loads read the
@@ -1719,6 +1792,12 @@ static bool stack_launch_ok(const ebpf_prog* p, const ebpf_batch* b, const ebpf_
 // variant.
 static bool stack_loop_ok(const ebpf_prog* p, const ebpf_batch* b, const ebpf_batch_out* out,
                           int device) {
+  // (a write-back batch: the loop kernel's stack variant has no write-back code, so only where
+  // no packet byte lies in the window -- fixed slots that end before it)
+  if ((b->flags & EBPF_BATCH_WRITEBACK) &&
+      (b->lens || b->offsets ||
+       b->stride + ((b->flags & EBPF_BATCH_XDP_MD) ? 8 : 0) > b->r10 - std::min<uint64_t>(b->r10, p->stack.k)))
+    return false;
   return stack_common_ok(p, b, out) && p->jit_mod[device][2] && stack_var_ok(p, b);
 }
 
@@ -1761,6 +1840,8 @@ static int batch_kind(const ebpf_prog* p, const ebpf_batch* b, const ebpf_batch_
 
 // The compiled program, where it applies (tile-kernel programs; same tables, same results).
 static const JitFns* batch_jit(ebpf_prog* p, const ebpf_batch* b, int kind, bool stk, int device) {
+  if (stk && kind != kKindLoop && (b->flags & EBPF_BATCH_WRITEBACK) && wb_needed(p))
+    return &p->wb_fn[device];
   if (stk) return &p->jit_fn[device][kind == kKindLoop ? 2 : 1];
   // (batch_kind routes a stack-window program to the loop kind without the stack flag only for
   // its promoted program)
@@ -1787,7 +1868,10 @@ static uint32_t kind_uops(const ebpf_prog* p, int kind) {
 
 static bool xdp_in_place(ebpf_prog* p, const ebpf_batch* b, bool mem_out, int device, int kind,
                          bool stk) {
-  if (!(b->flags & EBPF_BATCH_XDP_MD) || g_xdp_stage) return false;
+  // (a write-back batch never stages where it can run in place: a staged image's rewrite would
+  // stay in the workspace)
+  if (!(b->flags & EBPF_BATCH_XDP_MD) || (g_xdp_stage && !(b->flags & EBPF_BATCH_WRITEBACK)))
+    return false;
   // the general interpreter's tier 1 builds each lane's image [ctx][packet] itself (interp.hip);
   // so does its deopt pass after a store-mode launch
   if (kind == kKindTier1) return true;
@@ -1895,7 +1979,8 @@ static int check_batch(const ebpf_batch* b) {
   if (b->max_steps == 0) return EBPF_EINVAL;
   if (b->n && !b->frames) return EBPF_EINVAL;
   if (!b->offsets && b->stride == 0 && !b->lens) return EBPF_EINVAL;
-  if (b->flags & ~(EBPF_BATCH_GENERIC | EBPF_BATCH_XDP_MD | EBPF_BATCH_NO_JIT)) return EBPF_EINVAL;
+  if (b->flags & ~(EBPF_BATCH_GENERIC | EBPF_BATCH_XDP_MD | EBPF_BATCH_NO_JIT | EBPF_BATCH_WRITEBACK))
+    return EBPF_EINVAL;
   if ((b->flags & EBPF_BATCH_XDP_MD) &&
       (b->mem_size > 65528 || xdp_image_bytes(b) > 0xFFFFFFFFull))
     return EBPF_EINVAL;  // 8 + len must fit the u16 lengths; staged offsets are u32
@@ -1919,6 +2004,7 @@ int ebpf_run_batch(ebpf_prog* p, const ebpf_batch* bin, const ebpf_batch_out* ou
   const ebpf_batch* b = bin;
   rc = ebpf_prog_upload(p, device);
   if (rc) return rc;
+  if ((bin->flags & EBPF_BATCH_WRITEBACK) && wb_needed(p)) wb_upload(p, device);
   int cur = device_of_current();
   if (cur != device) hipSetDevice(device);
 
@@ -2004,6 +2090,7 @@ int ebpf_run_batch(ebpf_prog* p, const ebpf_batch* bin, const ebpf_batch_out* ou
   }
   a.regs_out = out->regs;
   a.xdp = xdp_direct ? 1u : 0u;
+  a.writeback = (bin->flags & EBPF_BATCH_WRITEBACK) ? 1u : 0u;  // (tier 1 and its deopt pass)
   a.init_fp = b->init_fp;
   a.init_fp_len = b->init_fp_len;
   a.fp_out = out->fp;
@@ -2091,6 +2178,7 @@ int ebpf_batch_kernel(ebpf_prog* p, const ebpf_batch* bin, const ebpf_batch_out*
   if (rc) return rc;
   rc = ebpf_prog_upload(p, device);
   if (rc) return rc;
+  if ((bin->flags & EBPF_BATCH_WRITEBACK) && wb_needed(p)) wb_upload(p, device);
   bool stk = false;
   const int kind = batch_kind(p, bin, out, device, &stk);
   ebpf_batch staged = *bin;  // xdp_md batches not run in place run as offsets + lens batches
@@ -2123,6 +2211,7 @@ int ebpf_batch_staged(ebpf_prog* p, const ebpf_batch* bin, const ebpf_batch_out*
   rc = ebpf_prog_upload(p, device);
   if (rc) return rc;
   if (!(bin->flags & EBPF_BATCH_XDP_MD)) return 0;
+  if ((bin->flags & EBPF_BATCH_WRITEBACK) && wb_needed(p)) wb_upload(p, device);
   bool stk = false;
   const int kind = batch_kind(p, bin, out, device, &stk);
   return xdp_in_place(p, bin, out->mem != nullptr, device, kind, stk) ||

@@ -966,6 +966,27 @@ __global__ __launch_bounds__(kBlock) void interp_kernel(LaunchArgs a) {
         put_image(mo, d, v, mem_size);
       }
     }
+    // write-back (EBPF_BATCH_WRITEBACK): a lane that ends OK stores its image's packet bytes back
+    // in place -- only the blocks a store materialised can differ from the packet -- dword by
+    // dword where the packet holds the whole dword at an aligned address, else byte by byte, so
+    // that no byte outside [0, len) of the packet is written. A lane that faulted writes nothing.
+    if (TIER == 1 && a.writeback && valid && st == EBPF_ST_OK && ib) {
+      uint8_t* const pk = const_cast<uint8_t*>(base);
+      const uint32_t lo = a.xdp ? 8u : 0u;  // (xdp_md: image byte 8 + i is packet byte i)
+      for (uint32_t blk = 0; blk < 32; blk++) {
+        if (!((ib >> blk) & 1u)) continue;
+        const uint32_t e1 = min((blk + 1) << bsh, (m_img + 3) / 4);
+        for (uint32_t e = blk << bsh; e < e1; e++) {
+          const uint32_t v = img[(size_t)e * kWave], o = e * 4;
+          if (o >= lo && o + 4 <= m_img && (((uintptr_t)(pk + (o - lo))) & 3) == 0) {
+            *(uint32_t*)(pk + (o - lo)) = v;
+          } else {
+            for (uint32_t i = 0; i < 4; i++)
+              if (o + i >= lo && o + i < m_img) pk[o + i - lo] = (uint8_t)(v >> (8 * i));
+          }
+        }
+      }
+    }
     if (TIER == 1 && valid && (a.fp_len_out || a.fp_out)) {  // the final frame stack (Emu.fp);
       if (a.fp_len_out) a.fp_len_out[pkt] = (uint8_t)csp;     // either output may come alone
       if (a.fp_out)

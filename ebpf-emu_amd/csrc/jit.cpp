@@ -1800,11 +1800,157 @@ struct Compiler {
     main += Z + ":\ns_mov_b64 exec, s[64:65]\ns_mov_b64 exec, 0\n";
     ovf_used = false;
     if (!copy(m, P, false, main, ool)) return false;
-    main += ".L" + P + "end:\n";
+    main += ".L" + P + "end:\n" + kWbMark;
     ool += overlay_routines() + ovf_routine();
     if (!ool.empty()) main += "s_branch .Ldone" + m.n + "\n" + ool;
-    out = peephole(main);
+    out = with_writeback(peephole(main), wb_store_mode(m, P));
     return true;
+  }
+
+  // ---- write-back (EBPF_BATCH_WRITEBACK: the program's variant 7, host.cpp) ----
+  // The rewritten packet bytes go back to the packet at the end of the program's code, before the
+  // statement's epilogue, for the lanes that end EBPF_ST_OK (a lane that faulted or deoptimized
+  // writes nothing: its stores were buffered in VGPRs, LDS or the overflow image, so its packet
+  // still holds the input bytes, which the deopt pass re-reads). Only this variant has the code:
+  // the statements (gen_tile.py) and every other variant's text are as they were.
+  bool wb = false;
+  static constexpr const char* kWbMark = "; @@WRITEBACK@@\n";
+  static std::string with_writeback(std::string text, const std::string& code) {
+    const size_t q = text.find(kWbMark);
+    if (q != std::string::npos) text.replace(q, strlen(kWbMark), code);
+    return text;
+  }
+  // Whether the statement behind m runs write-back batches: the fixed-slot statement and the var
+  // tile loop's (both name the xdp_md flag's SGPR); host.cpp routes the per-tile var kernel's
+  // batches (EBPF_KERNEL_JIT_VAR_STACK) to the general interpreter instead.
+  bool wb_here(const Marker& m) const { return wb && (m.fixed == "1" || m.varl) && !m.xdp.empty(); }
+  // the lanes that write back: s[60:61] = the packets of the tile (VM) whose status is 0
+  static std::string wb_lanes(const std::string& none) {
+    return "; write-back: the lanes that ended EBPF_ST_OK\n"
+           "s_mov_b64 exec, -1\nv_cmp_eq_u32 vcc, 0, v30\ns_and_b64 s[60:61], vcc, s[58:59]\n"
+           "s_cbranch_scc0 " + none + "\ns_mov_b64 exec, s[60:61]\n";
+  }
+  // The lanes of exec store the dwords v[64 + j] (j in `mask`) to v[46:47] + 4j, only the bytes
+  // below v48 (signed: what is left of the packet from v[46:47] on; a store at or past the packet's
+  // end is dropped). xs: the SGPR of the xdp_md flag -- when set, dwords 0 and 1 are the ctx and go
+  // nowhere -- or empty. Every lane with 64 bytes left: 16-byte stores; else per dword, whole where
+  // it fits and byte by byte in the lane's last dword, so that no byte of a neighbour is written.
+  // Keeps exec; uses v49-v51, s[64:67], vcc.
+  static std::string wb_dwords(uint32_t mask, const std::string& xs, const std::string& T) {
+    auto run = [](uint32_t cm, uint32_t c) {  // the dwords cm of chunk c, widest stores first
+      std::string s;
+      auto vr = [&](uint32_t a, uint32_t b) { return "v[" + std::to_string(64 + 4 * c + a) + ":" + std::to_string(64 + 4 * c + b) + "]"; };
+      if (cm == 15) return "global_store_dwordx4 v[46:47], " + vr(0, 3) + ", off offset:" + std::to_string(16 * c) + "\n";
+      for (uint32_t h = 0; h < 2; h++) {
+        const uint32_t pm = (cm >> (2 * h)) & 3;
+        if (pm == 3) {
+          s += "global_store_dwordx2 v[46:47], " + vr(2 * h, 2 * h + 1) + ", off offset:" + std::to_string(16 * c + 8 * h) + "\n";
+          continue;
+        }
+        for (uint32_t k = 0; k < 2; k++)
+          if (pm & (1u << k))
+            s += "global_store_dword v[46:47], v" + std::to_string(64 + 4 * c + 2 * h + k) + ", off offset:" +
+                 std::to_string(16 * c + 8 * h + 4 * k) + "\n";
+      }
+      return s;
+    };
+    std::string s = "s_mov_b64 s[64:65], exec\nv_cmp_gt_i32 vcc, 64, v48\ns_cbranch_vccnz .Lwbs" + T + "\n";
+    for (uint32_t c = 0; c < 4; c++) {
+      const uint32_t cm = (mask >> (4 * c)) & 15;
+      if (!cm) continue;
+      if (c == 0 && !xs.empty() && (cm & 3)) {
+        s += "s_cmp_lg_u32 " + xs + ", 0\ns_cbranch_scc1 .Lwbx" + T + "\n" + run(cm, 0) +
+             "s_branch .Lwby" + T + "\n.Lwbx" + T + ":\n" + run(cm & ~3u, 0) + ".Lwby" + T + ":\n";
+      } else {
+        s += run(cm, c);
+      }
+    }
+    s += "s_branch .Lwbd" + T + "\n.Lwbs" + T + ":\n";
+    for (uint32_t j = 0; j < 16; j++) {
+      if (!(mask & (1u << j))) continue;
+      const std::string J = std::to_string(j), V = "v" + std::to_string(64 + j), N = ".Lwbn" + J + T;
+      const std::string B = j & 1 ? "v51" : "v50";
+      if (j < 2 && !xs.empty()) s += "s_cmp_lg_u32 " + xs + ", 0\ns_cbranch_scc1 " + N + "\n";
+      s += "v_subrev_u32 v49, " + std::to_string(4 * j) + ", v48\n"
+           "v_cmp_le_i32 vcc, 4, v49\ns_and_b64 exec, s[64:65], vcc\n"
+           "global_store_dword v[46:47], " + V + ", off offset:" + std::to_string(4 * j) + "\n"
+           "s_mov_b64 exec, s[64:65]\n"
+           "v_cmp_gt_i32 vcc, 4, v49\nv_cmp_lt_i32 s[66:67], 0, v49\n"
+           "s_and_b64 exec, vcc, s[66:67]\ns_cbranch_execz " + N + "\n"
+           "global_store_byte v[46:47], " + V + ", off offset:" + std::to_string(4 * j) + "\n"
+           "v_lshrrev_b32 " + B + ", 8, " + V + "\n"
+           "v_cmp_lt_i32 vcc, 1, v49\ns_and_b64 exec, exec, vcc\n"
+           "global_store_byte v[46:47], " + B + ", off offset:" + std::to_string(4 * j + 1) + "\n"
+           "v_cmp_lt_i32 vcc, 2, v49\ns_and_b64 exec, exec, vcc\n"
+           "global_store_byte_d16_hi v[46:47], " + V + ", off offset:" + std::to_string(4 * j + 2) + "\n" +
+           N + ":\ns_mov_b64 exec, s[64:65]\n";
+    }
+    return s + ".Lwbd" + T + ":\ns_mov_b64 exec, s[64:65]\n";
+  }
+  // Store mode: the LDS header window (every dword: a register-address store may have written any)
+  // and then each filled 64-byte block of the lane's overflow image (v23's bits), read back from
+  // L2 (sc1, as the program's own loads of it) and stored at the packet's bytes [64 + 64b, ...).
+  std::string wb_store_mode(const Marker& m, const std::string& P) const {
+    if (!wb_here(m)) return "";
+    const std::string X = ".L" + P + "wbx";
+    std::string s = wb_lanes(X);
+    for (uint32_t c = 0; c < 4; c++)
+      s += "v_xad_u32 v" + std::to_string(36 + c) + ", v35, " + std::to_string(16 * c) + ", v34\n"
+           "ds_read_b128 v[" + std::to_string(64 + 4 * c) + ":" + std::to_string(67 + 4 * c) + "], v" +
+           std::to_string(36 + c) + "\n";
+    s += "v_lshl_add_u64 v[46:47], v[32:33], 0, 0\nv_mov_b32 v48, v31\ns_waitcnt lgkmcnt(0)\n" +
+         wb_dwords(0xffff, m.xdp, P + "w");
+    if (!dm.empty()) {
+      const std::string L = ".L" + P + "wbl";
+      s += "s_and_b64 s[60:61], s[60:61], " + dm + "\ns_cbranch_scc0 " + X + "\n"
+           "s_mov_b64 exec, s[60:61]\n" + ovf_addr() + "v_mov_b32 v52, v23\n" + L + ":\n"
+           "s_mov_b64 exec, s[60:61]\nv_cmp_ne_u32 vcc, 0, v52\ns_and_b64 exec, exec, vcc\n"
+           "s_cbranch_execz " + X + "\n"
+           "v_ffbl_b32 v39, v52\nv_lshlrev_b32 v40, v39, 1\nv_xor_b32 v52, v52, v40\n"
+           "v_lshlrev_b32 v40, 6, v39\nv_mov_b32 v41, 0\n"
+           "v_lshl_add_u64 v[42:43], v[44:45], 0, v[40:41]\n"
+           "v_add_u32 v40, 64, v40\n"
+           "v_lshl_add_u64 v[46:47], v[32:33], 0, v[40:41]\n"
+           "v_sub_u32 v48, v31, v40\n";
+      for (uint32_t c = 0; c < 4; c++)
+        s += "global_load_dwordx4 v[" + std::to_string(64 + 4 * c) + ":" + std::to_string(67 + 4 * c) +
+             "], v[42:43], off offset:" + std::to_string(16 * c) + " sc1\n";
+      s += "s_waitcnt vmcnt(0)\n" + wb_dwords(0xffff, "", P + "o") + "s_waitcnt vmcnt(0)\ns_branch " + L + "\n";
+    }
+    return s + X + ":\n" + wb_stack(P);
+  }
+  // The stack window's bytes that are packet bytes (a packet reaching past S0 = r10 - k, s57: the
+  // other layouts and store mode, stack_init): the window dwords of the lanes with LEN > S0, at
+  // the packet's bytes [S0, ...), below LEN only.
+  std::string wb_stack(const std::string& P) const {
+    static_assert(kStackMax == 64, "the window's dwords go through v[64:79], wb_dwords' 16");
+    const std::string Y = ".L" + P + "wby";
+    std::string s = "; write-back: the stack window's bytes of packets that reach into it\n"
+                    "s_mov_b64 exec, -1\nv_cmp_eq_u32 vcc, 0, v30\ns_and_b64 s[60:61], vcc, s[58:59]\n"
+                    "v_cmp_lt_u32 vcc, s57, v31\ns_and_b64 s[60:61], s[60:61], vcc\n"
+                    "s_cbranch_scc0 " + Y + "\ns_mov_b64 exec, s[60:61]\ns_waitcnt vmcnt(0)\n";
+    for (uint32_t j = 0; j < stk->k / 4; j++)
+      s += "v_mov_b32 v" + std::to_string(64 + j) + ", " + sv(j) + "\n";
+    s += "s_mov_b32 s48, s57\ns_mov_b32 s49, 0\nv_lshl_add_u64 v[46:47], v[32:33], 0, s[48:49]\n"
+         "v_subrev_u32 v48, s57, v31\n" +
+         wb_dwords(stk->k >= 64 ? 0xffffu : (1u << (stk->k / 4)) - 1, "", P + "s");
+    return s + Y + ":\n";
+  }
+  // Constant-address packet-window stores (no store mode): the dwords of v[64:79] some store of
+  // the program writes (known here; their other bytes are the packet's own, preloaded).
+  std::string wb_const(const Marker& m, const std::string& P) const {
+    if (!wb_here(m) || !stk) return "";
+    // (the fixed-slot statement runs these programs with the window past every packet byte,
+    // host.cpp stack_launch_ok: only the other layouts' packets can reach it)
+    if (!stk->any_pw) return m.fixed == "1" ? std::string() : wb_stack(P);
+    uint32_t mask = 0;
+    for (uint32_t i = 0; i < n; i++)
+      if (stk->pw[i] != kNoStack)
+        for (uint32_t b = (uint32_t)stk->pw[i]; b < (uint32_t)stk->pw[i] + uops[i].aux && b < 64; b++)
+          mask |= 1u << (b >> 2);
+    const std::string X = ".L" + P + "wbx";
+    return wb_lanes(X) + "v_lshl_add_u64 v[46:47], v[32:33], 0, 0\nv_mov_b32 v48, v31\n" +
+           wb_dwords(mask, m.xdp, P + "w") + X + ":\n" + (m.fixed == "1" ? std::string() : wb_stack(P));
   }
 
   // ATOMIC on the stack window at byte p = k + off (static, 4-aligned; 8 bytes read and written,
@@ -3369,6 +3515,8 @@ struct Compiler {
     // LDS, before any window read (LDS operations of a wave complete in order)
     bool reads_window = false;
     for (const Uop& o : uops) reads_window = reads_window || o.op == U_LDX;
+    // (write-back stores the window dwords a constant-address store merged into: shifted too)
+    if (wb && stk && stk->any_pw) reads_window = true;
     if ((m.fixed == "1" || m.varl) && reads_window && !m.xdp.empty() && !m.occ)
       main += "s_cmp_lg_u32 " + m.xdp + ", 0\ns_cbranch_scc0 .L" + P + "noxdp\n" + xdp_shift() +
               ".L" + P + "noxdp:\n";
@@ -3421,10 +3569,10 @@ struct Compiler {
       main += "s_mov_b64 exec, 0\n";
       if (!copy(m, P, false, main, ool)) return false;
     }
-    main += ".L" + P + "end:\n";
+    main += ".L" + P + "end:\n" + kWbMark;
     ool += overlay_routines();
     if (!ool.empty()) main += "s_branch .Ldone" + m.n + "\n" + ool;
-    out = peephole(main);
+    out = with_writeback(peephole(main), stk ? wb_const(m, P) : std::string());
     return true;
   }
 
@@ -4194,7 +4342,7 @@ bool store_mode_no_deopt(const std::vector<Uop>& uops, const StackPlan& stk, uin
 
 bool jit_compile(const std::vector<Uop>& uops, const std::vector<TUop>& t,
                  std::vector<char>& code_object, std::string* err, std::string* asm_out,
-                 const StackPlan* stk, bool* occ, bool main_layout) {
+                 const StackPlan* stk, bool* occ, bool main_layout, bool writeback) {
   if (uops.empty() || uops.size() > kJitMaxUops || t.size() < uops.size() ||
       (stk && (stk->k == 0 || stk->k > kStackMax || stk->k % 4 || stk->off.size() != uops.size() ||
                stk->pw.size() != uops.size() ||
@@ -4204,6 +4352,7 @@ bool jit_compile(const std::vector<Uop>& uops, const std::vector<TUop>& t,
   }
   Compiler c(uops, t, false, false, stk);
   c.main_layout = main_layout;
+  c.wb = writeback;
   const bool ok = compile_into_template(c, nullptr, code_object, err, asm_out);
   if (occ) *occ = ok && c.occ_ok;
   return ok;

@@ -104,9 +104,13 @@ constexpr uint32_t kStDeopt = 0x80;
 // code fits that statement's registers).
 // main_layout: the table of the main.rs register layout (variant 1): its compare narrowing may use
 // the load-time value ranges.
+// writeback: the write-back variant (EBPF_BATCH_WRITEBACK, host.cpp variant 7) of a stack-window
+// program with packet stores: the same code, then the rewritten packet bytes stored back to the
+// packets of the lanes that end EBPF_ST_OK (jit.cpp wb_store_mode / wb_const).
 bool jit_compile(const std::vector<Uop>& uops, const std::vector<TUop>& t,
                  std::vector<char>& code_object, std::string* err, std::string* asm_out = nullptr,
-                 const StackPlan* stk = nullptr, bool* occ = nullptr, bool main_layout = false);
+                 const StackPlan* stk = nullptr, bool* occ = nullptr, bool main_layout = false,
+                 bool writeback = false);
 
 // Loop programs (back edges, or budgets that can bind; tile tables of build_tile: `t` the block
 // table, `tx` the exact one-micro-op-per-block table) for ebpf_tile_jit_loop. *deep (if given):

@@ -101,6 +101,12 @@ struct LaunchArgs {
   uint32_t* deopt;
   uint32_t* deopt_idx;
   uint32_t deopt_pass;
+  // EBPF_BATCH_WRITEBACK on the general interpreter's tier 1 (the deopt pass included): a lane that
+  // ends EBPF_ST_OK stores its image's bytes [0, len) -- xdp_md: [8, 8 + len) -- back to its
+  // packet (the compiled store kernels' write-back variant does it in its own code, jit.cpp).
+  // (In the padding behind deopt_pass: the struct's layout, which the compiled statements read
+  // by offset, is unchanged.)
+  uint32_t writeback;
   // store mode on the var tile loop: per packet its image's bytes [64, 128) once it stores there
   // (u8[n][64] + 16 in the workspace past deopt_idx; jit.cpp ovf_fill), else null
   uint8_t* ovf;

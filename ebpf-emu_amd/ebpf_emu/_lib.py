@@ -27,6 +27,7 @@ DEFAULT_MEM, DEFAULT_R10, DEFAULT_STEPS = 1024, 512, 1 << 22
 BATCH_GENERIC = 1  # ebpf_batch.flags: EBPF_BATCH_GENERIC
 BATCH_XDP_MD = 2   # ebpf_batch.flags: EBPF_BATCH_XDP_MD (the xdp_md calling convention)
 BATCH_NO_JIT = 4   # ebpf_batch.flags: EBPF_BATCH_NO_JIT (the tile interpreter, not the compiled program)
+BATCH_WRITEBACK = 8  # ebpf_batch.flags: EBPF_BATCH_WRITEBACK (rewritten packets written back in place)
 MAX_CALL_DEPTH = 64
 # ebpf_batch_kernel ids (EBPF_KERNEL_*)
 (EBPF_KERNEL_GENERAL_T0, EBPF_KERNEL_GENERAL_T1, EBPF_KERNEL_DAG, EBPF_KERNEL_TILE,

@@ -180,7 +180,7 @@ class Program:
                    mem_size: int = _lib.DEFAULT_MEM, r10: int = _lib.DEFAULT_R10,
                    max_steps: int = _lib.DEFAULT_STEPS, init_regs=None,
                    workspace=None, generic: bool = False, xdp_md: bool = False,
-                   no_jit: bool = False, init_fp=None) -> _lib.Batch:
+                   no_jit: bool = False, init_fp=None, writeback: bool = False) -> _lib.Batch:
         b = _lib.Batch()
         _lib.lib().ebpf_batch_init(ctypes.byref(b))
         if n is None:
@@ -198,7 +198,8 @@ class Program:
             b.init_fp = init_fp.data_ptr()
             b.init_fp_len = init_fp.numel()
         b.flags = ((_lib.BATCH_GENERIC if generic else 0) | (_lib.BATCH_XDP_MD if xdp_md else 0) |
-                   (_lib.BATCH_NO_JIT if no_jit else 0))
+                   (_lib.BATCH_NO_JIT if no_jit else 0) |
+                   (_lib.BATCH_WRITEBACK if writeback else 0))
         if workspace is not None:
             b.workspace = workspace.data_ptr()
             b.workspace_bytes = workspace.numel() * workspace.element_size()
@@ -243,7 +244,7 @@ class Program:
             r0: bool = False, status: bool = False, counters=None, mem: bool = False,
             regs: bool = False, stream=None, generic: bool = False,
             xdp_md: bool = False, no_jit: bool = False, init_fp=None,
-            fp: bool = False) -> BatchResult:
+            fp: bool = False, writeback: bool = False) -> BatchResult:
         """Run the program over a device-resident batch; returns device tensors.
 
         frames: torch.uint8 CUDA tensor. Layout: packet i at frames[i*stride:] (stride layout,
@@ -255,12 +256,23 @@ class Program:
         every packet, bottom first; fp: return the final frame stacks (res.fp, res.fp_len).
         xdp_md: the xdp_md calling convention (EBPF_BATCH_XDP_MD): each image is
         [u32 data = 8][u32 data_end = 8 + len][packet], r1 = 0 the ctx, r2 = 8 + len.
+        writeback: EBPF_BATCH_WRITEBACK -- `frames` is written: every packet that ends ST_OK holds
+        its rewritten bytes [0, len) once the batch has completed on its stream, every other
+        packet and every byte outside the packets is untouched. Packets must not overlap; frames
+        must be a writable, contiguous tensor.
         """
         import torch
 
         dev = frames.device
+        if writeback:
+            if not frames.is_contiguous():
+                raise ValueError("writeback: frames must be contiguous (it is written in place)")
+            # (an inference tensor is torch's only read-only kind: in-place writes to it raise)
+            if frames.is_inference():
+                raise ValueError("writeback: frames must be writable (an inference tensor is not)")
         b = self.make_batch(frames, n, stride, offsets, lens, mem_size, r10, max_steps, init_regs,
-                            generic=generic, xdp_md=xdp_md, no_jit=no_jit, init_fp=init_fp)
+                            generic=generic, xdp_md=xdp_md, no_jit=no_jit, init_fp=init_fp,
+                            writeback=writeback)
         n = b.n
         res = BatchResult()
         if verdict:

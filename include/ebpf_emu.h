@@ -91,6 +91,20 @@ typedef struct ihipStream_t* ebpf_stream_t; /* == hipStream_t */
 /* ebpf_batch.flags: run a compiled program (ebpf_prog_compile) on the tile interpreter instead
  * (differential testing; results are identical by contract). */
 #define EBPF_BATCH_NO_JIT  4u
+/* ebpf_batch.flags: write each packet's rewrite back in place, as an XDP program rewrites the
+ * buffer the NIC then sends. `frames` is WRITTEN. Once the batch has completed on its stream:
+ *   - a packet with status EBPF_ST_OK holds the final image's bytes [0, len) (with
+ *     EBPF_BATCH_XDP_MD: image bytes [8, 8 + len); stores into the ctx words go nowhere);
+ *   - a packet with any other status (a fault, EBPF_ST_STEPS, EBPF_ST_BADPKT, EBPF_ST_JIT) holds
+ *     exactly its input bytes: a run is transactional per packet;
+ *   - no byte outside the packets is written: not the gaps between offsets-layout packets, not the
+ *     bytes of a stride slot past lens[i]; stores at image addresses >= len (the stack, a trailer
+ *     past a short packet) are dropped. In the stride layout without lens, len = stride.
+ * The caller's packets must not overlap (not checked). Every other output is bit-identical to the
+ * same batch without the flag, and out->mem may be requested as well. A program without stores
+ * runs the same kernel with and without the flag. (new: no reference counterpart; the reference
+ * runs one packet and prints r0) */
+#define EBPF_BATCH_WRITEBACK 8u
 #define EBPF_DEFAULT_MEM    1024   /* main.rs:16 */
 #define EBPF_DEFAULT_R10    512    /* main.rs:31 */
 #define EBPF_DEFAULT_STEPS  (1ull << 22)
@@ -99,7 +113,8 @@ typedef struct ihipStream_t* ebpf_stream_t; /* == hipStream_t */
  * Memory image per packet (main.rs:14-31 layout, sizes as launch parameters): mem_size zeroed
  * bytes, packet at [0,len), r1 = 0, r2 = len, r10 = r10, other registers 0. */
 typedef struct ebpf_batch {
-  const uint8_t* frames;    /* packet bytes */
+  const uint8_t* frames;    /* packet bytes (const: read only -- except with EBPF_BATCH_WRITEBACK,
+                               which writes the packets' rewritten bytes back through it) */
   const uint32_t* offsets;  /* packet i at frames + offsets[i]; NULL => frames + i*stride */
   const uint16_t* lens;     /* packet i length; NULL => stride */
   uint64_t stride;          /* bytes between packets in the stride layout, where frames must hold
@@ -107,7 +122,8 @@ typedef struct ebpf_batch {
   uint64_t n;               /* packets */
   uint32_t mem_size;        /* bytes of the per-packet memory image, 0..2^24 (any length: Mmu.memory
                                is a Vec<u8>, mmu.rs:2-4) */
-  uint32_t flags;           /* 0, or EBPF_BATCH_GENERIC | EBPF_BATCH_XDP_MD | EBPF_BATCH_NO_JIT */
+  uint32_t flags;           /* 0, or EBPF_BATCH_GENERIC | EBPF_BATCH_XDP_MD | EBPF_BATCH_NO_JIT |
+                               EBPF_BATCH_WRITEBACK */
   uint64_t r10;             /* initial r10 (stack top) */
   uint64_t max_steps;       /* per-packet step budget, 1..; faults EBPF_ST_STEPS beyond */
   void* workspace;          /* optional device scratch of ebpf_workspace_bytes() bytes, ZEROED before its
@@ -207,13 +223,19 @@ int ebpf_prog_compile(ebpf_prog* prog);
 
 /* The compiled program's gfx950 assembly (variant 0: forward-only, batches with init_regs; 1:
  * forward-only, the main.rs register layout, whose constant-address loads are resolved; 2: the
- * loop-program kernel), for inspection: copies up to cap bytes (NUL-terminated) and sets *len to
+ * loop-program kernel; 3: forward-only for xdp_md batches; 4: the stack-slot promoted loop
+ * program; 5, 6: the loop program for xdp_md batches, staged / in place; 7: the write-back
+ * variant -- variant 1 of a stack-window program with packet stores, followed by the stores of
+ * the rewritten packet bytes, EBPF_BATCH_WRITEBACK; compiled by the first request for it or the
+ * first batch with the flag), for inspection: copies up to cap bytes (NUL-terminated) and sets *len to
  * the full length. EBPF_EINVAL if that variant is not compiled. */
 int ebpf_prog_jit_asm(ebpf_prog* prog, int variant, char* buf, size_t cap, size_t* len);
 
 /* Why the program is not (wholly) compiled: compiles it first, then copies up to cap bytes
  * (NUL-terminated) of the reason -- the compiler's or assembler's error, or why the program is
  * not one the compiler takes -- and sets *len to its length; "" when every variant compiled.
+ * Once the write-back variant (7) has been asked for and failed, its reason is appended: such a
+ * program's EBPF_BATCH_WRITEBACK batches run the general interpreter (ebpf_batch_kernel says so).
  * (new: no reference counterpart; diagnostics for ebpf_prog_compile) */
 int ebpf_prog_jit_error(ebpf_prog* prog, char* buf, size_t cap, size_t* len);
 
@@ -242,7 +264,10 @@ int ebpf_run_batch(ebpf_prog* prog, const ebpf_batch* batch, const ebpf_batch_ou
 #define EBPF_KERNEL_JIT_VAR    6  /* compiled program, other layouts (ebpf_tile_jit_var) */
 #define EBPF_KERNEL_JIT_LOOP   7  /* compiled loop program (ebpf_tile_jit_loop) */
 #define EBPF_KERNEL_JIT_STACK  8  /* compiled stack-window program (memory tier 0.5, fixed slots;
-                                    store mode included) */
+                                    store mode included; with EBPF_BATCH_WRITEBACK its write-back
+                                    variant, as EBPF_KERNEL_JIT_VARL_STACK's -- a write-back batch
+                                    that would run EBPF_KERNEL_JIT_VAR_STACK runs
+                                    EBPF_KERNEL_GENERAL_T1 instead) */
 #define EBPF_KERNEL_JIT_VAR_STACK 9  /* compiled stack-window program, other layouts
                                         (ebpf_tile_jit_var_stack) */
 #define EBPF_KERNEL_JIT_LOOP_STACK 10 /* compiled stack-window loop program

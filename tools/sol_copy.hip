@@ -3,10 +3,13 @@
 //   grid   - a grid-stride float4 copy (every CU sweeping the buffer together), 4 loads in flight
 //   ranges - xdp_stage's shape: 4096 workgroups of 256 threads, each copying its own contiguous
 //            205 KB range (thread t: chunks t, t + 256, ..., four in flight)
+// `sol_copy BYTES` copies that many bytes instead (the write-back floor, DESIGN §3.36: a plain copy
+// of a batch's packet bytes, e.g. 67108864 for 1 Mi x 64 B).
 // HIP events around 10 launches each.  hipcc --offload-arch=gfx950 -O3 tools/sol_copy.hip -o build/sol_copy
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
+#include <cstdlib>
 
 __global__ __launch_bounds__(256) void copy_grid(const uint4* __restrict__ s, uint4* __restrict__ d, uint64_t n) {
   const uint64_t stride = (uint64_t)gridDim.x * 256;
@@ -31,8 +34,9 @@ __global__ __launch_bounds__(256) void copy_ranges(const uint4* __restrict__ s, 
   }
 }
 
-int main() {
-  const uint64_t bytes = 839647040ull, n = bytes / 16;
+int main(int argc, char** argv) {
+  const uint64_t bytes = argc > 1 ? strtoull(argv[1], nullptr, 10) / 16 * 16 : 839647040ull, n = bytes / 16;
+  if (!bytes) return 1;
   uint4 *s, *d;
   if (hipMalloc(&s, bytes) != hipSuccess || hipMalloc(&d, bytes) != hipSuccess) return 1;
   (void)hipMemset(s, 1, bytes);
