@@ -218,6 +218,19 @@ int device_of_current() {
   return d;
 }
 
+// Makes `device` the current one; the device that was current is so again when the scope ends.
+struct DeviceScope {
+  const int prev, dev;
+  explicit DeviceScope(int device) : prev(device_of_current()), dev(device) {
+    if (prev != dev) hipSetDevice(dev);
+  }
+  ~DeviceScope() {
+    if (prev != dev) hipSetDevice(prev);
+  }
+  DeviceScope(const DeviceScope&) = delete;
+  DeviceScope& operator=(const DeviceScope&) = delete;
+};
+
 }  // namespace
 
 struct ebpf_prog {
@@ -255,7 +268,8 @@ struct ebpf_prog {
   bool jit_has[kJitVariants] = {};
   bool jit_occ[kJitVariants] = {};  // the variant's code also went into ebpf_tile_jit_fixed_occ
   std::vector<char> jit_co[kJitVariants];
-  bool jit_deep = false;  // variant 2 compiled into ebpf_tile_jit_loop_deep
+  bool jit_deep[kJitVariants] = {};  // a loop variant (2, 4, 5, 6) compiled into
+                                     // ebpf_tile_jit_loop_deep
   std::string jit_asm[kJitVariants];
   std::string jit_err;
   hipModule_t jit_mod[kMaxDevices][kJitVariants] = {};
@@ -274,9 +288,6 @@ struct ebpf_prog {
   TUop* dev_pltuops[kMaxDevices] = {};
   TUop* dev_pltuopsx[kMaxDevices] = {};
   uint32_t pguard_k = 0;
-  bool pjit_deep = false;  // variant 4 compiled into ebpf_tile_jit_loop_deep
-  bool xjit_deep = false;  // variant 5 likewise
-  bool rjit_deep = false;  // variant 6 likewise
   // the write-back variant (EBPF_BATCH_WRITEBACK; ebpf_prog_jit_asm's variant 7): variant 1's
   // program of a stack-window program with packet stores, its code followed by the stores of the
   // rewritten packet bytes (jit.cpp wb_store_mode / wb_const). Compiled on the first use of the
@@ -424,9 +435,7 @@ static int jit_compile_locked(ebpf_prog* p) {
         p->jit_co[v] = std::move(r[v].co);
         p->jit_asm[v] = std::move(r[v].text);
         p->jit_occ[v] = r[v].occ;
-        bool* deep = v == 2 ? &p->jit_deep : v == 4 ? &p->pjit_deep : v == 5 ? &p->xjit_deep
-                     : v == 6 ? &p->rjit_deep : nullptr;
-        if (deep) *deep = r[v].deep;
+        p->jit_deep[v] = r[v].deep;
       };
       for (int v = 0; v < kJitVariants && p->jit_state == 1; v++) {
         if (!p->jit_has[v]) continue;
@@ -512,8 +521,7 @@ static bool wb_compile_locked(ebpf_prog* p) {
 static void wb_upload(ebpf_prog* p, int device) {
   std::lock_guard<std::mutex> lk(p->mu);
   if (p->wb_mod[device] || !wb_compile_locked(p)) return;
-  int cur = device_of_current();
-  if (cur != device) hipSetDevice(device);
+  DeviceScope on(device);
   if (jit_load(p->wb_co, &p->wb_mod[device], &p->wb_fn[device])) {
     p->wb_fn[device].var_only = false;
     p->wb_fn[device].fixed_occ = p->wb_fn[device].fixed_occw = nullptr;
@@ -523,7 +531,6 @@ static void wb_upload(ebpf_prog* p, int device) {
     p->wb_co.clear();
     p->wb_err = "write-back variant: the code object did not load";
   }
-  if (cur != device) hipSetDevice(cur);
 }
 
 // Length-binned lane packing for the loop-mode tile kernel (EBPFEMU_BIN=0|1 forces it off/on;
@@ -1664,9 +1671,8 @@ int ebpf_prog_upload(ebpf_prog* p, int device) {
       if (p->jit_has[v]) {
         if (!jit_load(p->jit_co[v], &p->jit_mod[device][v], &p->jit_fn[device][v]))
           rc = EBPF_EHIP;
-        else if ((v == 2 && p->jit_deep) || (v == 4 && p->pjit_deep) ||
-                 (v == 5 && p->xjit_deep) || (v == 6 && p->rjit_deep))  // (the code is in the
-          p->jit_fn[device][v].loop = p->jit_fn[device][v].loop_deep;     // deep-prefetch kernel)
+        else if (p->jit_deep[v])  // (the code is in the deep-prefetch kernel)
+          p->jit_fn[device][v].loop = p->jit_fn[device][v].loop_deep;
         // (store mode runs on the fixed-slot statement too since round 6: gen_tile.py st=1)
         p->jit_fn[device][v].var_only = false;
         if (!p->jit_occ[v]) p->jit_fn[device][v].fixed_occ = p->jit_fn[device][v].fixed_occw = nullptr;
@@ -1749,32 +1755,25 @@ static bool stack_var_ok(const ebpf_prog* p, const ebpf_batch* b) {
 }
 
 // Forward stack-window programs on the compiled forward kernels (fixed slots: the window must lie
-// past every packet byte, so it starts as zeros; other layouts: stack_var_ok).
+// past every packet byte, so it starts as zeros; other layouts: stack_var_ok). l: the batch's layout.
 static bool stack_launch_ok(const ebpf_prog* p, const ebpf_batch* b, const ebpf_batch_out* out,
-                            int device) {
+                            int device, const BatchLayout& l) {
   // (a write-back batch of a program with packet stores: the write-back variant's code)
   const bool wbv = (b->flags & EBPF_BATCH_WRITEBACK) && wb_needed(p);
   if (!stack_common_ok(p, b, out) || !(wbv ? p->wb_mod[device] : p->jit_mod[device][1]) ||
       b->max_steps < p->xuops.size())
     return false;
   const uint64_t k = p->stack.k, r10 = b->r10;
-  LaunchArgs la{};
-  la.frames = b->frames;
-  la.offsets = b->offsets;
-  la.lens = b->lens;
-  la.stride = b->stride;
-  la.mem_out = out->mem;
   // (store mode runs on the var kernel whatever the layout: its window init covers any packet;
   // its header-window loads read LDS without a bounds check, so the image must cover the window)
-  const bool fixed = launch_fixed_layout(la) && !p->stack.any_dyn;
+  const bool fixed = launch_fixed_layout(l) && !p->stack.any_dyn;
   const uint64_t img_len = b->stride + ((b->flags & EBPF_BATCH_XDP_MD) ? 8 : 0);
   if (fixed ? r10 - k < img_len : !stack_var_ok(p, b)) return false;
   if (p->stack.any_dyn && b->mem_size < (uint64_t)kWin) return false;
   if (wbv) {  // the write-back code is in the two tile loops' statements: the per-tile var kernel's
               // batches (unaligned metadata, ...) write back on the general interpreter
-    la.n_uops = (uint32_t)p->xuops.size();
-    la.n_tiles = (b->n + 63) / 64;
-    const int id = launch_kernel_id(kKindDag, la, &p->wb_fn[device], true);
+    const int id =
+        launch_kernel_id(kKindDag, (uint32_t)p->xuops.size(), l, &p->wb_fn[device], true);
     if (id != EBPF_KERNEL_JIT_STACK && id != EBPF_KERNEL_JIT_VARL_STACK) return false;
   }
   for (const auto& kl : p->kloads) {
@@ -1816,14 +1815,14 @@ static bool promo_ok(const ebpf_prog* p, const ebpf_batch* b, const ebpf_batch_o
 // step budget that can bind (exact budget); a stack-window batch runs the compiled stack kernels
 // (forward, or the loop kernel's) or the general interpreter.
 static int batch_kind(const ebpf_prog* p, const ebpf_batch* b, const ebpf_batch_out* out,
-                      int device, bool* stk) {
+                      int device, const BatchLayout& l, bool* stk) {
   // (the final frame stacks of a flattened program are its copies' stacks: the general
   // interpreter's frame stack writes them)
   const bool generic = (b->flags & EBPF_BATCH_GENERIC) || b->init_fp_len ||
                        (p->flattened && (out->fp || out->fp_len));
   *stk = false;
   if (p->stack.k && !generic) {
-    if (stack_launch_ok(p, b, out, device)) return *stk = true, kKindDag;
+    if (stack_launch_ok(p, b, out, device, l)) return *stk = true, kKindDag;
     if (promo_ok(p, b, out, device)) return kKindLoop;  // (stk false: the promoted program)
     if (stack_loop_ok(p, b, out, device)) return *stk = true, kKindLoop;
     return batch_tier(p, b);
@@ -1838,20 +1837,25 @@ static int batch_kind(const ebpf_prog* p, const ebpf_batch* b, const ebpf_batch_
                                                                          : batch_tier(p, b);
 }
 
-// The compiled program, where it applies (tile-kernel programs; same tables, same results).
-static const JitFns* batch_jit(ebpf_prog* p, const ebpf_batch* b, int kind, bool stk, int device) {
-  if (stk && kind != kKindLoop && (b->flags & EBPF_BATCH_WRITEBACK) && wb_needed(p))
-    return &p->wb_fn[device];
-  if (stk) return &p->jit_fn[device][kind == kKindLoop ? 2 : 1];
+// The compiled variant of a batch of this kind, where one applies (tile-kernel programs; same
+// tables, same results): its index, kJitVariantWb for the write-back variant, -1 for none. flags,
+// init_regs: of the batch the kernel sees (a staged xdp_md batch: without EBPF_BATCH_XDP_MD).
+static int batch_variant(const ebpf_prog* p, uint32_t flags, bool init_regs, int kind, bool stk,
+                         int device) {
+  if (stk && kind != kKindLoop && (flags & EBPF_BATCH_WRITEBACK) && wb_needed(p))
+    return kJitVariantWb;
+  if (stk) return kind == kKindLoop ? 2 : 1;
   // (batch_kind routes a stack-window program to the loop kind without the stack flag only for
   // its promoted program)
-  if (kind == kKindLoop && p->stack.k) return &p->jit_fn[device][4];
-  if (b->flags & EBPF_BATCH_NO_JIT) return nullptr;
+  if (kind == kKindLoop && p->stack.k) return 4;
+  if (flags & EBPF_BATCH_NO_JIT) return -1;
   if (kind == kKindDag && p->jit_mod[device][0])
-    return &p->jit_fn[device][b->init_regs ? 0
-                              : (b->flags & EBPF_BATCH_XDP_MD) && p->jit_mod[device][3] ? 3 : 1];
-  if (kind == kKindLoop && p->jit_mod[device][2]) return &p->jit_fn[device][2];
-  return nullptr;
+    return init_regs ? 0 : (flags & EBPF_BATCH_XDP_MD) && p->jit_mod[device][3] ? 3 : 1;
+  if (kind == kKindLoop && p->jit_mod[device][2]) return 2;
+  return -1;
+}
+static const JitFns* variant_fns(const ebpf_prog* p, int device, int v) {
+  return v < 0 ? nullptr : v == kJitVariantWb ? &p->wb_fn[device] : &p->jit_fn[device][v];
 }
 
 // The micro-ops a kernel kind runs: the general interpreter the decoded program's, every other
@@ -1865,42 +1869,31 @@ static uint32_t kind_uops(const ebpf_prog* p, int kind) {
 // xdp_window, jit.cpp xdp_shift) and read the packet 8 bytes further on; every other kernel runs
 // the images xdp_stage writes into the workspace. EBPFEMU_XDP_STAGE=1 stages always (A/B runs:
 // g_xdp_stage, defined outside this extern "C" block).
-
-static bool xdp_in_place(ebpf_prog* p, const ebpf_batch* b, bool mem_out, int device, int kind,
-                         bool stk) {
+// id: the kernel of the batch in place (l: its layout, xdp set: not the occupancy variant).
+static bool xdp_in_place(const ebpf_batch* b, int kind, int id, const BatchLayout& l) {
   // (a write-back batch never stages where it can run in place: a staged image's rewrite would
   // stay in the workspace)
-  if (!(b->flags & EBPF_BATCH_XDP_MD) || (g_xdp_stage && !(b->flags & EBPF_BATCH_WRITEBACK)))
-    return false;
+  if (g_xdp_stage && !(b->flags & EBPF_BATCH_WRITEBACK)) return false;
   // the general interpreter's tier 1 builds each lane's image [ctx][packet] itself (interp.hip);
   // so does its deopt pass after a store-mode launch
   if (kind == kKindTier1) return true;
   if (kind != kKindDag) return false;
-  LaunchArgs a{};
-  a.n_uops = kind_uops(p, kind);
-  a.frames = b->frames;
-  a.offsets = b->offsets;
-  a.lens = b->lens;
-  a.stride = b->stride;
-  a.n_tiles = (b->n + 63) / 64;
-  a.mem_out = mem_out ? (uint8_t*)16 : nullptr;
-  a.xdp = 1;  // (the route of an xdp_md batch in place: not the occupancy variant)
-  const int id = launch_kernel_id(kind, a, batch_jit(p, b, kind, stk, device), stk);
   return id == EBPF_KERNEL_JIT_FIXED || id == EBPF_KERNEL_JIT_VAR ||
          id == EBPF_KERNEL_JIT_STACK || id == EBPF_KERNEL_JIT_VAR_STACK ||
          id == EBPF_KERNEL_JIT_VARL || id == EBPF_KERNEL_JIT_VARL_STACK ||
-         (id == EBPF_KERNEL_TILE && !launch_fixed_layout(a));
+         (id == EBPF_KERNEL_TILE && !launch_fixed_layout(l));
 }
 
 // An xdp_md batch of a loop program in place (no staging copy): variant 6, the program rebased
 // (jit.cpp Compiler::xdp_rebase; compiled only when every packet load is proven past the ctx),
 // runs the batch as the main.rs layout over the packets with mem_size - 8 (rebased_batch). Not
 // with final images (they hold the ctx) or caller-set registers (the proofs assume r1 = the ctx).
-static bool xdp_rebased(ebpf_prog* p, const ebpf_batch* b, const ebpf_batch_out* out, int device,
-                        int kind, bool stk) {
-  if (!(b->flags & EBPF_BATCH_XDP_MD) || g_xdp_stage || kind != kKindLoop || stk) return false;
+// variant: the batch's compiled variant (the plain loop program's).
+static bool xdp_rebased(const ebpf_prog* p, const ebpf_batch* b, const ebpf_batch_out* out,
+                        int device, int kind, bool stk, int variant) {
+  if (g_xdp_stage || kind != kKindLoop || stk) return false;
   if (!p->jit_mod[device][6] || out->mem || b->init_regs || b->mem_size < 8) return false;
-  return batch_jit(p, b, kind, stk, device) == &p->jit_fn[device][2];
+  return variant == 2;
 }
 static ebpf_batch rebased_batch(const ebpf_batch* b) {
   ebpf_batch r = *b;
@@ -1911,11 +1904,9 @@ static ebpf_batch rebased_batch(const ebpf_batch* b) {
 
 // The general interpreter's tier-1 grid for a batch (its wave slots' images: the workspace).
 static int tier1_grid(const ebpf_prog* p, const ebpf_batch* b, int device) {
-  int cur = device_of_current();
-  hipSetDevice(device);
+  DeviceScope on(device);
   int grid = 0;
   interp_grid(kKindTier1, (uint32_t)p->uops.size(), p->tiny, (b->n + 63) / 64, &grid);
-  hipSetDevice(cur);
   return grid;
 }
 
@@ -1923,26 +1914,44 @@ static int tier1_grid(const ebpf_prog* p, const ebpf_batch* b, int device) {
 // empty list; each of its workgroups stages the program and flushes its counters)
 constexpr int kDeoptMaxGrid = 256;
 
-// Bytes of the tier-1 wave slots (workspace, from kWsSlotsOff).
-static uint64_t tier1_slots_bytes(const ebpf_prog* p, const ebpf_batch* b, int device) {
-  if (batch_tier(p, b) != 1) return 0;
-  return (uint64_t)tier1_grid(p, b, device) * kWavesPerBlock * tier1_slot_bytes(b->mem_size);
+// Where a batch's regions lie in its workspace (byte offsets; launch.h has the fixed head below
+// kWsSlotsOff). The binned order and the tier-1 wave slots share their start (no kernel uses
+// both at once), the deopt list's indices follow whichever of the two the batch uses, the
+// overflow images follow the indices, and the xdp_md staging region is the last xdp bytes.
+// total reserves for any compiled variant: the binned order whether or not this batch is
+// binned, and the slots and the order both.
+struct WsLayout {
+  uint64_t bin_off, slots_off, deopt_idx_off, ovf_off, xdp_off, total;
+  int t1_grid;  // the tier-1 grid the slots are sized for; 0: not a tier-1 batch, not asked for
+};
+
+// b: the batch as the caller gave it, or rebased (rebased_batch: no staging region); binned:
+// whether it runs in binned order (only the placement of the indices depends on it).
+static WsLayout ws_layout(const ebpf_prog* p, const ebpf_batch* b, int device, bool binned) {
+  WsLayout w{};
+  // the binned packet order, then the per-workgroup class counts
+  const uint64_t bin_bytes = b->n * 4 + 4ull * kBinMaxWgs * kBinClasses;
+  // (the occupancy query behind the grid: only for the batches that have slots)
+  w.t1_grid = batch_tier(p, b) == 1 ? tier1_grid(p, b, device) : 0;
+  const uint64_t slots = (uint64_t)w.t1_grid * kWavesPerBlock * tier1_slot_bytes(b->mem_size);
+  w.bin_off = w.slots_off = kWsSlotsOff;
+  w.deopt_idx_off = kWsSlotsOff + align16(std::max<uint64_t>(slots, binned ? bin_bytes : 0));
+  w.ovf_off = w.deopt_idx_off + align16(b->n * 4);
+  uint64_t end = kWsSlotsOff;
+  if (use_binning(p, b)) end += align16(bin_bytes);  // (either loop program of a promoted stack
+                                                      // program may run)
+  end += align16(slots);
+  if (p->stack.any_dyn || !p->puops.empty()) end += align16(b->n * 4);  // the deopt list's indices
+  if (p->stack.any_dyn)  // store mode: the overflow images (jit.h ovf_stride)
+    end += b->n * ovf_stride(b->mem_size) + 16;
+  w.xdp_off = end;
+  w.total = end + ((b->flags & EBPF_BATCH_XDP_MD) ? xdp_region_bytes(b) : 0);
+  return w;
 }
 
 uint64_t ebpf_workspace_bytes(const ebpf_prog* p, const ebpf_batch* b, int device) {
   if (!p || !b) return 0;
-  const uint64_t x = (b->flags & EBPF_BATCH_XDP_MD) ? xdp_region_bytes(b) : 0;
-  uint64_t bytes = kWsSlotsOff + x;
-  // the binned packet order, then the per-workgroup class counts (either loop program of a
-  // promoted stack program may run)
-  if (use_binning(p, b))
-    bytes += align16(b->n * 4 + 4ull * kBinMaxWgs * kBinClasses);
-  bytes += align16(tier1_slots_bytes(p, b, device));
-  if (p->stack.any_dyn || !p->puops.empty())  // the deopt list's indices (past the slots)
-    bytes += align16(b->n * 4);
-  if (p->stack.any_dyn)  // store mode: the overflow images (past the indices; jit.h ovf_stride)
-    bytes += b->n * ovf_stride(b->mem_size) + 16;
-  return bytes;  // (the xdp_md region, when present, is the last x bytes)
+  return ws_layout(p, b, device, false).total;
 }
 
 // The batch's workspace of `need` bytes on `device` (current): the caller's, or the library-owned
@@ -1987,6 +1996,114 @@ static int check_batch(const ebpf_batch* b) {
   return EBPF_OK;
 }
 
+// Where and how a batch runs: everything ebpf_run_batch works out before and between its
+// launches, decided once by plan_batch. ebpf_run_batch executes the plan; ebpf_batch_kernel and
+// ebpf_batch_staged report from it.
+enum XdpMode : int { kXdpNone = 0, kXdpInPlace, kXdpRebased, kXdpStaged };
+enum DeoptMode : int {
+  kDeoptNone = 0,    // not a deopt launch
+  kDeoptPass = 1,    // the general interpreter's pass over the deopt list follows
+  kDeoptNoPass = 2,  // lanes may be listed by the kernel's code, but none can leave: no pass
+                     // (LaunchArgs::deopt_pass = 2 on the compiled launch)
+};
+struct BatchPlan {
+  int kind = kKindTier0;       // KernelKind
+  bool stk = false;            // a memory tier 0.5 batch on the compiled stack kernels
+  bool promo = false;          // the stack-slot promoted program's tables
+  int variant = -1;            // the compiled variant that runs: -1 none, kJitVariantWb write-back
+  const JitFns* jit = nullptr; //   ... and its kernels on the device
+  int kernel_id = 0;           // EBPF_KERNEL_*
+  XdpMode xdp = kXdpNone;
+  // the batch the kernel sees: the caller's; rebased (rebased_batch); or staged -- offsets + lens
+  // without EBPF_BATCH_XDP_MD, its frames, offsets and lens filled in once the workspace is known
+  ebpf_batch eff;
+  BatchLayout layout;          // of eff
+  bool deep = false;           // the loop variant's code is in ebpf_tile_jit_loop_deep
+  bool binned = false;         // length-binned order (launch_binning before the kernel)
+  DeoptMode deopt = kDeoptNone;
+  WsLayout ws;
+  int grid = 0;                // the main launch's (interp_grid)
+  int pass_grid = 0;           // kDeoptPass: the pass's
+};
+
+// Plans `bin` with outputs `out` for the uploaded program on `device`, which is current. The
+// only reader of the batch's flags, the StackPlan, the loaded variants and the environment
+// switches for any of BatchPlan's fields. No launch, no allocation; the HIP calls are the
+// occupancy queries behind the grids (cached per kernel).
+static int plan_batch(const ebpf_prog* p, const ebpf_batch* bin, const ebpf_batch_out* out,
+                      int device, BatchPlan* plan) {
+  BatchPlan& r = *plan;
+  const uint64_t n_tiles = (bin->n + 63) / 64;
+  BatchLayout l = batch_layout(bin->frames, bin->offsets, bin->lens, bin->stride, n_tiles,
+                               out->mem != nullptr, false);
+  r.kind = batch_kind(p, bin, out, device, l, &r.stk);
+  // (the stack-slot promoted program: batch_kind's loop kind without the stack flag)
+  r.promo = r.kind == kKindLoop && !r.stk && p->stack.k;
+  const uint32_t n_uops = kind_uops(p, r.kind);
+  r.variant = batch_variant(p, bin->flags, bin->init_regs != nullptr, r.kind, r.stk, device);
+  r.eff = *bin;
+  if (bin->flags & EBPF_BATCH_XDP_MD) {
+    l.xdp = true;
+    const int id = launch_kernel_id(r.kind, n_uops, l, variant_fns(p, device, r.variant), r.stk);
+    if (xdp_in_place(bin, r.kind, id, l)) {
+      r.xdp = kXdpInPlace;
+    } else if (xdp_rebased(p, bin, out, device, r.kind, r.stk, r.variant)) {
+      r.xdp = kXdpRebased;  // (the batch run as the main.rs layout: no staging region)
+      r.eff = rebased_batch(bin);
+      r.variant = 6;
+      l.xdp = false;
+    } else {
+      r.xdp = kXdpStaged;  // offsets + lens, written into the (16-byte aligned) workspace
+      l = BatchLayout();
+      l.offsets = l.lens = true;
+      l.mem_out = out->mem != nullptr;
+      l.n_tiles = n_tiles;
+      r.variant = batch_variant(p, bin->flags & ~EBPF_BATCH_XDP_MD, bin->init_regs != nullptr,
+                                r.kind, r.stk, device);
+      // (variant 5, whose range analysis knows the staged images' ctx, compiles ctx loads
+      // through r1 as the ctx's constants: only with the main.rs registers, r1 = the image start)
+      if (r.variant == 2 && !bin->init_regs && p->jit_mod[device][5]) r.variant = 5;
+    }
+  }
+  r.jit = variant_fns(p, device, r.variant);
+  r.deep = r.variant >= 0 && r.variant < kJitVariants && p->jit_deep[r.variant];
+  // (eff is still the caller's batch or the rebased one: what the workspace is sized from)
+  r.binned = r.kind == kKindLoop && use_binning(p, &r.eff, r.deep);
+  r.ws = ws_layout(p, &r.eff, device, r.binned);
+  if (r.xdp == kXdpStaged) {
+    r.eff.stride = 0;
+    r.eff.flags &= ~EBPF_BATCH_XDP_MD;
+  }
+  r.layout = l;
+  const int id = r.kernel_id = launch_kernel_id(r.kind, n_uops, l, r.jit, r.stk);
+  // store mode (register-address packet stores, StackPlan::any_dyn): lanes the compiled kernel
+  // cannot finish are listed, then re-run from the start by the general interpreter (tier 1)
+  // (the promoted program: lanes whose packet reaches the slots, jit.cpp promo_guard)
+  const bool deopt = r.jit && ((r.stk && p->stack.any_dyn && r.kind == kKindDag &&
+                                (id == EBPF_KERNEL_JIT_VAR_STACK ||
+                                 id == EBPF_KERNEL_JIT_VARL_STACK || id == EBPF_KERNEL_JIT_STACK)) ||
+                               r.promo);
+  if (deopt) {
+    const ebpf_batch& b = r.eff;
+    // store mode on the var tile loop with no lane able to leave (StackPlan::no_deopt: the main.rs
+    // registers, the stack window at or past the overflow image's end): no deopt pass
+    const uint64_t s0 = b.r10 >= p->stack.k ? b.r10 - p->stack.k : 0;  // the stack window's start
+    // (the longest image a lane can have: the slot of a batch without lengths, else mem_size --
+    // an access bounded by LEN must end before the stack window)
+    const uint64_t len_max = std::min<uint64_t>(
+        b.mem_size, !l.lens && !l.offsets ? b.stride + (l.xdp ? 8 : 0) : b.mem_size);
+    // (a store ending past mem_size faults before it could deoptimize: bounded by mem_size too)
+    const bool no_pass =
+        (id == EBPF_KERNEL_JIT_VARL_STACK || id == EBPF_KERNEL_JIT_STACK) && p->stack.no_deopt &&
+        !b.init_regs && s0 >= std::min<uint64_t>(p->stack.st_bound, b.mem_size) &&
+        (!p->stack.len_bound || (b.mem_size <= kOvfEnd && s0 >= len_max));
+    r.deopt = no_pass ? kDeoptNoPass : kDeoptPass;
+    if (!no_pass)
+      r.pass_grid = std::min(r.ws.t1_grid ? r.ws.t1_grid : tier1_grid(p, &b, device), kDeoptMaxGrid);
+  }
+  return interp_grid(r.kind, n_uops, p->tiny, n_tiles, &r.grid) == 0 ? EBPF_OK : EBPF_EHIP;
+}
+
 int ebpf_run_batch(ebpf_prog* p, const ebpf_batch* bin, const ebpf_batch_out* out,
                    ebpf_stream_t stream) {
   if (!p || !out) return EBPF_EINVAL;
@@ -2000,82 +2117,57 @@ int ebpf_run_batch(ebpf_prog* p, const ebpf_batch* bin, const ebpf_batch_out* ou
     device = device_of_current();
   }
   if (bin->n == 0) return EBPF_OK;
-  ebpf_batch staged = *bin;  // an xdp_md batch runs as the staged offsets + lens batch
-  const ebpf_batch* b = bin;
   rc = ebpf_prog_upload(p, device);
   if (rc) return rc;
   if ((bin->flags & EBPF_BATCH_WRITEBACK) && wb_needed(p)) wb_upload(p, device);
-  int cur = device_of_current();
-  if (cur != device) hipSetDevice(device);
-
-  const uint64_t n_tiles = (b->n + 63) / 64;
-  bool stk = false;
-  const int kind = batch_kind(p, b, out, device, &stk);
-  int grid = 0;
-  if (interp_grid(kind, kind_uops(p, kind), p->tiny, n_tiles, &grid) != 0) {
-    if (cur != device) hipSetDevice(cur);
-    return EBPF_EHIP;
-  }
-  const bool xdp_direct = xdp_in_place(p, bin, out->mem != nullptr, device, kind, stk);
-  const bool xdp_rb = !xdp_direct && xdp_rebased(p, bin, out, device, kind, stk);
-  if (xdp_rb) {  // (the batch run as the main.rs layout: no staging region)
-    staged = rebased_batch(bin);
-    b = &staged;
-  }
+  DeviceScope on(device);
+  BatchPlan plan;
+  rc = plan_batch(p, bin, out, device, &plan);
+  if (rc) return rc;
   // scratch: caller-provided or library-owned per (device, stream)
-  const uint64_t need = ebpf_workspace_bytes(p, b, device);
   uint8_t* ws = nullptr;
-  rc = batch_workspace(bin, need, device, s, &ws);
-  if (rc) {
-    if (cur != device) hipSetDevice(cur);
-    return rc;
-  }
-  if ((bin->flags & EBPF_BATCH_XDP_MD) && !xdp_direct && !xdp_rb) {
-    uint8_t* x = ws + need - xdp_region_bytes(bin);
+  rc = batch_workspace(bin, plan.ws.total, device, s, &ws);
+  if (rc) return rc;
+  ebpf_batch& b = plan.eff;
+  if (plan.xdp == kXdpStaged) {  // offsets u32[n], lengths u16[n], then the images
+    uint8_t* x = ws + plan.ws.xdp_off;
     uint32_t* doffs = (uint32_t*)x;
     uint16_t* dlens = (uint16_t*)(x + align16(bin->n * 4));
     uint8_t* dst = x + align16(bin->n * 4) + align16(bin->n * 2);
     unsigned long long* cursor = (unsigned long long*)(ws + kWsXdpCursorOff);
     if (hipMemsetAsync(cursor, 0, 8, s) != hipSuccess ||
         launch_xdp_stage(bin->frames, bin->offsets, bin->lens, bin->stride, bin->n, bin->mem_size,
-                         dst, doffs, dlens, cursor, s) != hipSuccess) {
-      if (cur != device) hipSetDevice(cur);
+                         dst, doffs, dlens, cursor, s) != hipSuccess)
       return EBPF_EHIP;
-    }
-    staged.frames = dst;
-    staged.offsets = doffs;
-    staged.lens = dlens;
-    staged.stride = 0;
-    staged.flags &= ~EBPF_BATCH_XDP_MD;
-    b = &staged;
+    b.frames = dst;
+    b.offsets = doffs;
+    b.lens = dlens;
   }
   LaunchArgs a{};
   a.prog = p->dev_uops[device];
   // constant-address loads are resolved for the main.rs register layout only
-  a.dprog = b->init_regs ? p->dev_duops[device] : p->dev_duopsk[device];
-  // (the stack-slot promoted program: batch_kind's loop kind without the stack flag)
-  const bool promo = kind == kKindLoop && !stk && p->stack.k;
-  a.tprog = promo ? p->dev_pltuops[device]
-           : kind == kKindLoop ? p->dev_ltuops[device]
-           : b->init_regs      ? p->dev_tuops[device] : p->dev_tuopsk[device];
-  a.tprog_exact = promo ? p->dev_pltuopsx[device] : p->dev_ltuopsx[device];
-  a.n_uops = kind_uops(p, kind);
-  a.mem_size = b->mem_size;
-  a.frames = b->frames;
-  a.offsets = b->offsets;
-  a.lens = b->lens;
-  a.stride = b->stride;
-  a.n = b->n;
-  a.r10 = b->r10;
-  a.max_steps = b->max_steps;
+  a.dprog = b.init_regs ? p->dev_duops[device] : p->dev_duopsk[device];
+  a.tprog = plan.promo ? p->dev_pltuops[device]
+           : plan.kind == kKindLoop ? p->dev_ltuops[device]
+           : b.init_regs            ? p->dev_tuops[device] : p->dev_tuopsk[device];
+  a.tprog_exact = plan.promo ? p->dev_pltuopsx[device] : p->dev_ltuopsx[device];
+  a.n_uops = kind_uops(p, plan.kind);
+  a.mem_size = b.mem_size;
+  a.frames = b.frames;
+  a.offsets = b.offsets;
+  a.lens = b.lens;
+  a.stride = b.stride;
+  a.n = b.n;
+  a.r10 = b.r10;
+  a.max_steps = b.max_steps;
   a.verdict = out->verdict;
   a.r0 = out->r0;
   a.status = out->status;
   a.counters = out->counters;
   a.shards = (uint64_t*)(ws + kWsShardsOff);
-  a.image_ws = ws + kWsSlotsOff;
-  a.n_tiles = n_tiles;
-  a.init_regs = b->init_regs;
+  a.image_ws = ws + plan.ws.slots_off;
+  a.n_tiles = plan.layout.n_tiles;
+  a.init_regs = b.init_regs;
   a.mem_out = out->mem;
   if (g_trace) {  // a ring of kTraceRing launches' stamps
     const size_t tb = kTraceWaves * kTraceSlots * sizeof(uint64_t);
@@ -2089,135 +2181,68 @@ int ebpf_run_batch(ebpf_prog* p, const ebpf_batch* bin, const ebpf_batch_out* ou
                                           (kTraceWaves * kTraceSlots);
   }
   a.regs_out = out->regs;
-  a.xdp = xdp_direct ? 1u : 0u;
+  a.xdp = plan.xdp == kXdpInPlace ? 1u : 0u;
   a.writeback = (bin->flags & EBPF_BATCH_WRITEBACK) ? 1u : 0u;  // (tier 1 and its deopt pass)
-  a.init_fp = b->init_fp;
-  a.init_fp_len = b->init_fp_len;
+  a.init_fp = b.init_fp;
+  a.init_fp_len = b.init_fp_len;
   a.fp_out = out->fp;
   a.fp_len_out = out->fp_len;
   // only the tier-1 kernel has a frame stack; every other kernel runs programs without CALL and
   // with an empty initial stack, whose final stack is empty
-  if (kind != kKindTier1 && out->fp_len && hipMemsetAsync(out->fp_len, 0, b->n, s) != hipSuccess) {
-    if (cur != device) hipSetDevice(cur);
+  if (plan.kind != kKindTier1 && out->fp_len && hipMemsetAsync(out->fp_len, 0, b.n, s) != hipSuccess)
     return EBPF_EHIP;
-  }
-  // the compiled variant that runs: variant 4 for the promoted program, 6 for an xdp_md batch in
-  // place (rebased), 5 for a staged one (its range analysis knows the staged images' ctx)
-  const JitFns* jit = xdp_rb ? &p->jit_fn[device][6] : batch_jit(p, b, kind, stk, device);
-  // (variant 5 compiles ctx loads through r1 as the ctx's constants: only with the main.rs
-  // registers, r1 = the image start)
-  if (jit == &p->jit_fn[device][2] && (bin->flags & EBPF_BATCH_XDP_MD) && !xdp_direct &&
-      !b->init_regs && p->jit_mod[device][5])
-    jit = &p->jit_fn[device][5];
-  const bool deep = jit == &p->jit_fn[device][2]   ? p->jit_deep
-                    : jit == &p->jit_fn[device][4] ? p->pjit_deep
-                    : jit == &p->jit_fn[device][5] ? p->xjit_deep
-                    : jit == &p->jit_fn[device][6] ? p->rjit_deep
-                                                   : false;
-  if (kind == kKindLoop && use_binning(p, b, deep)) {
-    a.perm = (const uint32_t*)(ws + kWsSlotsOff);
+  if (plan.binned) {
+    a.perm = (const uint32_t*)(ws + plan.ws.bin_off);
     a.bin_counts = (uint32_t*)(ws + kWsBinCountsOff);
-    if (launch_binning(b->lens, b->n, (uint32_t*)a.perm + b->n, (uint32_t*)a.perm, s) !=
-        hipSuccess) {
-      if (cur != device) hipSetDevice(cur);
+    if (launch_binning(b.lens, b.n, (uint32_t*)a.perm + b.n, (uint32_t*)a.perm, s) != hipSuccess)
       return EBPF_EHIP;
-    }
   }
-  // store mode (register-address packet stores, StackPlan::any_dyn): lanes the compiled kernel
-  // cannot finish are listed, then re-run from the start by the general interpreter (tier 1)
-  // (the promoted program: lanes whose packet reaches the slots, jit.cpp promo_guard)
-  const int kid = jit ? launch_kernel_id(kind, a, jit, stk) : -1;
-  const bool deopt = (stk && p->stack.any_dyn && kind == kKindDag && jit &&
-                      (kid == EBPF_KERNEL_JIT_VAR_STACK || kid == EBPF_KERNEL_JIT_VARL_STACK ||
-                       kid == EBPF_KERNEL_JIT_STACK)) ||
-                     (promo && jit);
-  // store mode on the var tile loop with no lane able to leave (StackPlan::no_deopt: the main.rs
-  // registers, the stack window at or past the overflow image's end): no deopt pass
-  const uint64_t s0 = b->r10 >= p->stack.k ? b->r10 - p->stack.k : 0;  // the stack window's start
-  // (the longest image a lane can have: the slot of a batch without lengths, else mem_size --
-  // an access bounded by LEN must end before the stack window)
-  const uint64_t len_max = std::min<uint64_t>(
-      b->mem_size, !b->lens && !b->offsets ? b->stride + (a.xdp ? 8 : 0) : b->mem_size);
-  // (a store ending past mem_size faults before it could deoptimize: bounded by mem_size too)
-  const bool pass = deopt && !((kid == EBPF_KERNEL_JIT_VARL_STACK || kid == EBPF_KERNEL_JIT_STACK) &&
-                               p->stack.no_deopt &&
-                               !b->init_regs &&
-                               s0 >= std::min<uint64_t>(p->stack.st_bound, b->mem_size) &&
-                               (!p->stack.len_bound ||
-                                (b->mem_size <= kOvfEnd && s0 >= len_max)));
-  if (deopt) {
+  if (plan.deopt != kDeoptNone) {
     a.deopt = (uint32_t*)(ws + kWsDeoptOff);
-    // (past the tier-1 slots, or the binned order and its class counts when the batch is binned)
-    const uint64_t bin_bytes = a.perm ? b->n * 4 + 4ull * kBinMaxWgs * kBinClasses : 0;
-    a.deopt_idx = (uint32_t*)(ws + kWsSlotsOff +
-                              align16(std::max<uint64_t>(tier1_slots_bytes(p, b, device), bin_bytes)));
-    if (p->stack.any_dyn) a.ovf = (uint8_t*)a.deopt_idx + align16(b->n * 4);
-    if (!pass) a.deopt_pass = 2;  // (no pass follows: a lane that leaves faults EBPF_ST_JIT)
+    a.deopt_idx = (uint32_t*)(ws + plan.ws.deopt_idx_off);
+    if (p->stack.any_dyn) a.ovf = ws + plan.ws.ovf_off;
+    // (no pass follows: a lane that leaves faults EBPF_ST_JIT)
+    if (plan.deopt == kDeoptNoPass) a.deopt_pass = 2;
   }
-  hipError_t e = launch_interp(kind, a, grid, s, jit, stk);
-  if (pass && e == hipSuccess) {
-    LaunchArgs d = a;
+  hipError_t e = launch_interp(plan.kernel_id, a, plan.grid, s, plan.jit);
+  if (plan.deopt == kDeoptPass && e == hipSuccess) {
+    LaunchArgs d = a;  // (xdp_md in place: tier 1 builds the ctx-prefixed images itself)
     d.deopt_pass = 1;
     d.n_uops = (uint32_t)p->uops.size();
     d.tprog = d.tprog_exact = nullptr;
     d.dprog = nullptr;
-    d.xdp = a.xdp;  // (in place: tier 1 builds the ctx-prefixed images itself)
-    const int g1 = std::min(tier1_grid(p, b, device), kDeoptMaxGrid);
-    e = launch_interp(kKindTier1, d, g1, s, nullptr, false);
+    e = launch_interp(EBPF_KERNEL_GENERAL_T1, d, plan.pass_grid, s);
     // a failed pass leaves the list's count behind: the next batch's pass would re-run its stale
     // indices (the pass's last workgroup clears count and done)
     if (e != hipSuccess) (void)hipMemsetAsync(a.deopt, 0, 8, s);
   }
-  if (cur != device) hipSetDevice(cur);
   return e == hipSuccess ? EBPF_OK : EBPF_EHIP;
 }
 
-int ebpf_batch_kernel(ebpf_prog* p, const ebpf_batch* bin, const ebpf_batch_out* out, int device) {
+// The plan ebpf_run_batch would execute for this batch on `device` (the queries' common part:
+// the program is uploaded there first, as a run would).
+static int query_plan(ebpf_prog* p, const ebpf_batch* bin, const ebpf_batch_out* out, int device,
+                      BatchPlan* plan) {
   if (!p || !out || device < 0 || device >= kMaxDevices) return EBPF_EINVAL;
   int rc = check_batch(bin);
   if (rc) return rc;
   rc = ebpf_prog_upload(p, device);
   if (rc) return rc;
   if ((bin->flags & EBPF_BATCH_WRITEBACK) && wb_needed(p)) wb_upload(p, device);
-  bool stk = false;
-  const int kind = batch_kind(p, bin, out, device, &stk);
-  ebpf_batch staged = *bin;  // xdp_md batches not run in place run as offsets + lens batches
-  const bool rb = xdp_rebased(p, bin, out, device, kind, stk);
-  if (rb) {
-    staged = rebased_batch(bin);
-  } else if ((bin->flags & EBPF_BATCH_XDP_MD) &&
-             !xdp_in_place(p, bin, out->mem != nullptr, device, kind, stk)) {
-    staged.offsets = (const uint32_t*)16;
-    staged.lens = (const uint16_t*)16;
-    staged.stride = 0;
-    staged.flags &= ~EBPF_BATCH_XDP_MD;
-  }
-  LaunchArgs a{};
-  a.n_uops = kind_uops(p, kind);
-  a.frames = staged.frames;
-  a.offsets = staged.offsets;
-  a.lens = staged.lens;
-  a.stride = staged.stride;
-  a.mem_out = out->mem;
-  a.xdp = (staged.flags & EBPF_BATCH_XDP_MD) && !rb ? 1u : 0u;  // (in place: as ebpf_run_batch)
-  return launch_kernel_id(kind, a, rb ? &p->jit_fn[device][6] : batch_jit(p, &staged, kind, stk, device),
-                          stk);
+  DeviceScope on(device);
+  return plan_batch(p, bin, out, device, plan);
+}
+
+int ebpf_batch_kernel(ebpf_prog* p, const ebpf_batch* bin, const ebpf_batch_out* out, int device) {
+  BatchPlan plan;
+  const int rc = query_plan(p, bin, out, device, &plan);
+  return rc ? rc : plan.kernel_id;
 }
 
 int ebpf_batch_staged(ebpf_prog* p, const ebpf_batch* bin, const ebpf_batch_out* out, int device) {
-  if (!p || !out || device < 0 || device >= kMaxDevices) return EBPF_EINVAL;
-  int rc = check_batch(bin);
-  if (rc) return rc;
-  rc = ebpf_prog_upload(p, device);
-  if (rc) return rc;
-  if (!(bin->flags & EBPF_BATCH_XDP_MD)) return 0;
-  if ((bin->flags & EBPF_BATCH_WRITEBACK) && wb_needed(p)) wb_upload(p, device);
-  bool stk = false;
-  const int kind = batch_kind(p, bin, out, device, &stk);
-  return xdp_in_place(p, bin, out->mem != nullptr, device, kind, stk) ||
-                 xdp_rebased(p, bin, out, device, kind, stk)
-             ? 0
-             : 1;
+  BatchPlan plan;
+  const int rc = query_plan(p, bin, out, device, &plan);
+  return rc ? rc : plan.xdp == kXdpStaged ? 1 : 0;
 }
 
 int ebpf_run_batch_multi(ebpf_prog* p, int nshards, const int* devices, const ebpf_batch* batches,

@@ -2285,23 +2285,20 @@ static bool tile_kernel_for(int kind, uint32_t n_uops) {
 }
 
 // The tile kernel's lean variant serves the fixed-slot stride layout without image output.
-static bool fixed_layout(const LaunchArgs* a) {
-  return a && a->offsets == nullptr && a->lens == nullptr && a->mem_out == nullptr &&
-         a->stride >= (uint64_t)kWin && (((uintptr_t)a->frames | (uintptr_t)a->stride) & 15) == 0;
+bool launch_fixed_layout(const BatchLayout& l) {
+  return !l.offsets && !l.lens && !l.mem_out && l.stride >= (uint64_t)kWin && l.slots16;
 }
-
-bool launch_fixed_layout(const LaunchArgs& a) { return fixed_layout(&a); }
 
 // The compiled fixed-slot kernel keeps tile indices and tile byte offsets in 32-bit scalars.
-static bool jit_fixed_layout(const LaunchArgs* a) {
-  return fixed_layout(a) && a->n_tiles < (1ull << 31) && a->stride < (1ull << 26);
+static bool jit_fixed_layout(const BatchLayout& l) {
+  return launch_fixed_layout(l) && l.n_tiles < (1ull << 31) && l.stride < (1ull << 26);
 }
 
-static const void* kernel_for(int kind, uint32_t n_uops, const LaunchArgs* a = nullptr) {
+// The interpreter kernel of a kind; fixed: the tile kernel's lean fixed-slot variant.
+static const void* kernel_for(int kind, uint32_t n_uops, bool fixed = false) {
   if (kind == kKindDag) {
     if (tile_kernel_for(kind, n_uops))
-      return fixed_layout(a) ? (const void*)tile_kernel<true, false>
-                             : (const void*)tile_kernel<false, false>;
+      return fixed ? (const void*)tile_kernel<true, false> : (const void*)tile_kernel<false, false>;
     return n_uops > 64 ? (const void*)dag_kernel<4> : (const void*)dag_kernel<1>;
   }
   if (kind == kKindLoop) return (const void*)tile_kernel<false, true>;
@@ -2410,99 +2407,131 @@ static bool jit_forward_for(int kind, uint32_t n_uops) {
 // offsets (4-byte aligned) or 16-byte aligned slots of >= 64 bytes, lengths 4-byte aligned or
 // absent, no final images, tile indices in 31 bits (store-mode programs with their deopt list
 // included).
-static bool varl_ok(int kind, const LaunchArgs& a, const JitFns* jit, bool stack) {
-  const bool layout = a.offsets ? ((uintptr_t)a.offsets & 3) == 0
-                                : a.stride >= (uint64_t)kWin && a.stride < (1ull << 26) &&
-                                      (((uintptr_t)a.frames | (uintptr_t)a.stride) & 15) == 0;
+static bool varl_ok(int kind, uint32_t n_uops, const BatchLayout& l, const JitFns* jit,
+                    bool stack) {
+  const bool layout = l.offsets ? l.offsets4
+                                : l.stride >= (uint64_t)kWin && l.stride < (1ull << 26) && l.slots16;
   // (the fixed-slot layout's programs keep ebpf_tile_jit_fixed; store-mode programs, which run
   // on the var kernels only, are stack-window programs)
-  return jit && jit->varl && kind == kKindDag && jit_forward_for(kind, a.n_uops) &&
-         layout && ((uintptr_t)a.lens & 3) == 0 && !a.mem_out && !a.perm &&
-         a.n_tiles < (1ull << 31) && (!jit_fixed_layout(&a) || jit->var_only) &&
-         (!jit->var_only || stack);
+  return jit && jit->varl && kind == kKindDag && jit_forward_for(kind, n_uops) && layout &&
+         l.lens4 && !l.mem_out && l.n_tiles < (1ull << 31) &&
+         (!jit_fixed_layout(l) || jit->var_only) && (!jit->var_only || stack);
 }
 
 // The fixed-slot kernel's occupancy variant takes a compiled issue-bound program's fixed-slot
 // batches (jit_compile's *occ; not stack-window programs, not xdp_md in place: its code has no
 // preloaded window to shift the ctx into).
-static bool fixed_occ_ok(int kind, const LaunchArgs& a, const JitFns* jit, bool stack) {
-  return jit && jit->fixed_occ && !stack && !jit->var_only && !a.xdp && kind == kKindDag &&
-         jit_forward_for(kind, a.n_uops) && jit_fixed_layout(&a);
+static bool fixed_occ_ok(int kind, uint32_t n_uops, const BatchLayout& l, const JitFns* jit,
+                         bool stack) {
+  return jit && jit->fixed_occ && !stack && !jit->var_only && !l.xdp && kind == kKindDag &&
+         jit_forward_for(kind, n_uops) && jit_fixed_layout(l);
 }
 
-int launch_kernel_id(int kind, const LaunchArgs& a, const JitFns* jit, bool stack) {
+int launch_kernel_id(int kind, uint32_t n_uops, const BatchLayout& l, const JitFns* jit,
+                     bool stack) {
   if (jit && jit->loop && kind == kKindLoop)
     return stack ? EBPF_KERNEL_JIT_LOOP_STACK : EBPF_KERNEL_JIT_LOOP;
-  if (varl_ok(kind, a, jit, stack))
+  if (varl_ok(kind, n_uops, l, jit, stack))
     return stack ? EBPF_KERNEL_JIT_VARL_STACK : EBPF_KERNEL_JIT_VARL;
-  if (fixed_occ_ok(kind, a, jit, stack)) return EBPF_KERNEL_JIT_FIXED_OCC;
-  if (jit && jit->fixed && jit_forward_for(kind, a.n_uops))
-    return jit_fixed_layout(&a) && !jit->var_only
+  if (fixed_occ_ok(kind, n_uops, l, jit, stack)) return EBPF_KERNEL_JIT_FIXED_OCC;
+  if (jit && jit->fixed && jit_forward_for(kind, n_uops))
+    return jit_fixed_layout(l) && !jit->var_only
                ? (stack ? EBPF_KERNEL_JIT_STACK : EBPF_KERNEL_JIT_FIXED)
-                                : (stack ? EBPF_KERNEL_JIT_VAR_STACK : EBPF_KERNEL_JIT_VAR);
+               : (stack ? EBPF_KERNEL_JIT_VAR_STACK : EBPF_KERNEL_JIT_VAR);
   if (kind == kKindDag)
-    return tile_kernel_for(kind, a.n_uops) ? EBPF_KERNEL_TILE : EBPF_KERNEL_DAG;
+    return tile_kernel_for(kind, n_uops) ? EBPF_KERNEL_TILE : EBPF_KERNEL_DAG;
   if (kind == kKindLoop) return EBPF_KERNEL_TILE_LOOP;
   return kind == kKindTier1 ? EBPF_KERNEL_GENERAL_T1 : EBPF_KERNEL_GENERAL_T0;
 }
 
-hipError_t launch_interp(int kind, const LaunchArgs& a, int grid, hipStream_t stream,
-                         const JitFns* jit, bool stack) {
-  const uint32_t lds = lds_bytes_for(kind, a.n_uops, jit && jit->loop);
-  // the compiled var kernels: balanced persistent waves at their own occupancy (interp_grid sizes
-  // for tile_kernel's, which is higher: its extra workgroups would run in a second round)
-  const bool var = jit && jit->fixed && kind != kKindLoop && jit_forward_for(kind, a.n_uops) &&
-                   (!jit_fixed_layout(&a) || jit->var_only);
-  const uint32_t vlds = kWavesPerBlock * kVarWaveLds;
-  if (var) grid = jit_grid(stack ? jit->var_stack : jit->var, vlds, a.n_tiles);
-  const bool vl = varl_ok(kind, a, jit, stack);
-  const uint32_t llds = kWavesPerBlock * kVarlWaveLds;
-  if (vl) {
-    grid = jit_grid(stack ? jit->varl_stack : jit->varl, llds, a.n_tiles);
-    // (tests: EBPFEMU_VARL_WGS caps the workgroups, so a moderate batch gives each wave more than
-    // the 511 tiles of one statement entry)
-    const char* cap = getenv("EBPFEMU_VARL_WGS");
-    if (cap && atoi(cap) > 0 && atoi(cap) < grid) grid = atoi(cap);
+hipError_t launch_interp(int id, const LaunchArgs& a, int grid, hipStream_t stream,
+                         const JitFns* jit) {
+  // The id names the function, the block, the LDS bytes and the grid rule. k: an interpreter
+  // kernel of this library, f: a compiled kernel of the program's module (a stack-window
+  // program's ids take its _stack function). lgrid: the launch's grid where it is not `grid`.
+  const void* k = nullptr;
+  hipFunction_t f = nullptr;
+  uint32_t block = kBlock, lds = 0;
+  int kind = kKindDag, lgrid = -1;
+  switch (id) {
+    case EBPF_KERNEL_GENERAL_T0:
+    case EBPF_KERNEL_GENERAL_T1:
+      kind = id == EBPF_KERNEL_GENERAL_T1 ? kKindTier1 : kKindTier0;
+      k = kernel_for(kind, a.n_uops);
+      lds = lds_bytes_for(kind, a.n_uops);
+      break;
+    case EBPF_KERNEL_DAG:
+    case EBPF_KERNEL_TILE:
+      k = kernel_for(kKindDag, a.n_uops,
+                     launch_fixed_layout(batch_layout(a.frames, a.offsets, a.lens, a.stride,
+                                                      a.n_tiles, a.mem_out != nullptr, a.xdp)));
+      lds = lds_bytes_for(kKindDag, a.n_uops);
+      break;
+    case EBPF_KERNEL_TILE_LOOP:
+      kind = kKindLoop;
+      k = kernel_for(kKindLoop, a.n_uops);
+      lds = lds_bytes_for(kKindLoop, a.n_uops);
+      break;
+    case EBPF_KERNEL_JIT_LOOP:
+    case EBPF_KERNEL_JIT_LOOP_STACK:  // the compiled loop program
+      kind = kKindLoop;
+      f = id == EBPF_KERNEL_JIT_LOOP_STACK ? jit->loop_stack : jit->loop;
+      lds = lds_bytes_for(kKindLoop, a.n_uops, true);
+      break;
+    case EBPF_KERNEL_JIT_VARL:
+    case EBPF_KERNEL_JIT_VARL_STACK: {  // offsets + lens batches: the var tile loop
+      f = id == EBPF_KERNEL_JIT_VARL_STACK ? jit->varl_stack : jit->varl;
+      lds = kWavesPerBlock * kVarlWaveLds;
+      grid = jit_grid(f, lds, a.n_tiles);
+      // (tests: EBPFEMU_VARL_WGS caps the workgroups, so a moderate batch gives each wave more than
+      // the 511 tiles of one statement entry)
+      const char* cap = getenv("EBPFEMU_VARL_WGS");
+      if (cap && atoi(cap) > 0 && atoi(cap) < grid) grid = atoi(cap);
+      break;
+    }
+    case EBPF_KERNEL_JIT_FIXED_OCC: {  // one window buffer, 6 waves per SIMD
+      const bool wide = a.n_uops >= kOccWideUops;  // (jit.cpp compiled the code into that one)
+      f = wide ? jit->fixed_occw : jit->fixed_occ;
+      block = wide ? kOccWideBlock : kOccBlock;
+      lds = (wide ? kOccWideWaves : kOccWaves) * kWinBytes;
+      lgrid = jit_grid(f, lds, a.n_tiles, block, true, wide ? kOccWideWgsPerCu : kOccWgsPerCu);
+      break;
+    }
+    case EBPF_KERNEL_JIT_FIXED:
+    case EBPF_KERNEL_JIT_STACK:  // double-buffered windows: its own LDS size and grid
+      f = jit->fixed;
+      block = kDbBlock;
+      lds = kDbWaves * kTileWaveLdsDb;
+      lgrid = jit_grid(f, lds, a.n_tiles, kDbBlock, true);
+      break;
+    case EBPF_KERNEL_JIT_VAR:
+    case EBPF_KERNEL_JIT_VAR_STACK:
+      // balanced persistent waves at the var kernel's own occupancy (interp_grid sizes for
+      // tile_kernel's, which is higher: its extra workgroups would run in a second round); the
+      // tile kernel's window LDS + a second metadata buffer, also for programs past kTileMaxUops
+      f = id == EBPF_KERNEL_JIT_VAR_STACK ? jit->var_stack : jit->var;
+      lds = kWavesPerBlock * kVarWaveLds;
+      grid = jit_grid(f, lds, a.n_tiles);
+      break;
+    default:
+      return hipErrorInvalidValue;
   }
   LaunchArgs b = a;
   // a shard word's sum must stay below 2^48: bound it by packets x steps per packet; and its
   // arrival count (16 bits) must reach the shard's workgroups - 1: at most 65535 members (the
-  // compiled fixed-slot kernel's grid is one workgroup per CU, every other grid is `grid`)
+  // compiled fixed-slot kernels' own grid, lgrid, is one workgroup per resident slot; every other
+  // grid is `grid`)
   const uint64_t steps = kind == kKindDag ? (uint64_t)a.n_uops : a.max_steps;
   const uint64_t members = ((uint64_t)grid + kCounterShards - 1) / kCounterShards;
   const bool fits = a.n < (1ull << 40) && steps < (1ull << 47) / (a.n + 1) &&
                     members < (1ull << (64 - kShardCountShift));
   const bool fold_kernel = g_fold_kernel || !fits;
   b.fold_kernel = fold_kernel ? 1u : 0u;
+  if (lgrid < 0) lgrid = grid;
   void* bargs[] = {(void*)&b};
-  hipError_t e;
-  if (jit && jit->loop && kind == kKindLoop) {  // the compiled loop program
-    e = hipModuleLaunchKernel(stack ? jit->loop_stack : jit->loop, grid, 1, 1, kBlock, 1, 1, lds,
-                              stream, bargs, nullptr);
-  } else if (vl) {  // offsets + lens batches: the var tile loop
-    e = hipModuleLaunchKernel(stack ? jit->varl_stack : jit->varl, grid, 1, 1, kBlock, 1, 1, llds,
-                              stream, bargs, nullptr);
-  } else if (fixed_occ_ok(kind, a, jit, stack)) {  // one window buffer, 6 waves per SIMD
-    const bool wide = a.n_uops >= kOccWideUops;  // (jit.cpp compiled the code into that one)
-    hipFunction_t f = wide ? jit->fixed_occw : jit->fixed_occ;
-    const uint32_t ob = wide ? kOccWideBlock : kOccBlock;
-    const uint32_t olds = (wide ? kOccWideWaves : kOccWaves) * kWinBytes;
-    e = hipModuleLaunchKernel(f, jit_grid(f, olds, a.n_tiles, ob, true,
-                                          wide ? kOccWideWgsPerCu : kOccWgsPerCu), 1, 1,
-                              ob, 1, 1, olds, stream, bargs, nullptr);
-  } else if (jit && jit->fixed && jit_forward_for(kind, a.n_uops)) {
-    if (jit_fixed_layout(&a) && !jit->var_only) {  // double-buffered windows: its own LDS size and grid
-      const uint32_t dlds = kDbWaves * kTileWaveLdsDb;
-      e = hipModuleLaunchKernel(jit->fixed, jit_grid(jit->fixed, dlds, a.n_tiles, kDbBlock, true),
-                                1, 1, kDbBlock, 1, 1, dlds, stream, bargs, nullptr);
-    } else {  // (the tile kernel's window LDS + a second metadata buffer, also for programs
-              // past kTileMaxUops)
-      e = hipModuleLaunchKernel(stack ? jit->var_stack : jit->var, grid, 1, 1, kBlock, 1, 1, vlds,
-                                stream, bargs, nullptr);
-    }
-  } else
-    e = hipLaunchKernel(kernel_for(kind, a.n_uops, &a), dim3(grid), dim3(kBlock), bargs, lds,
-                        stream);
+  const hipError_t e =
+      f ? hipModuleLaunchKernel(f, lgrid, 1, 1, block, 1, 1, lds, stream, bargs, nullptr)
+        : hipLaunchKernel(k, dim3(lgrid), dim3(block), bargs, lds, stream);
   if (e != hipSuccess || a.counters == nullptr || !fold_kernel) return e;
   uint64_t* shards = a.shards;
   uint64_t* counters = a.counters;

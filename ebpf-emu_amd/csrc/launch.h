@@ -145,20 +145,51 @@ hipError_t launch_xdp_stage(const uint8_t* frames, const uint32_t* offsets, cons
                             uint32_t* doffs, uint16_t* dlens, unsigned long long* cursor,
                             hipStream_t stream);
 
-// Whether a launch runs the fixed-slot kernels (stride layout, 16-byte aligned slots of >= 64
-// bytes, no lengths, no image output; EBPFEMU_FIXED=0 disables them).
-bool launch_fixed_layout(const LaunchArgs& a);
+// What of a batch's layout picks its kernel: everything launch_kernel_id reads of a batch. Taken
+// from the batch's pointers (batch_layout), or stated outright for a batch whose arrays do not
+// exist yet (host.cpp: the staged form of an xdp_md batch, whose offsets and lengths the library
+// writes into its 16-byte aligned workspace).
+struct BatchLayout {
+  bool offsets = false, lens = false;  // the arrays are present
+  bool offsets4 = true, lens4 = true;  //   ... and 4-byte aligned (true when absent)
+  bool slots16 = false;                // frames and stride are both 16-byte aligned
+  bool mem_out = false;                // the final images are an output
+  bool xdp = false;                    // xdp_md in place (LaunchArgs::xdp)
+  uint64_t stride = 0;
+  uint64_t n_tiles = 0;
+};
+inline BatchLayout batch_layout(const uint8_t* frames, const uint32_t* offsets,
+                                const uint16_t* lens, uint64_t stride, uint64_t n_tiles,
+                                bool mem_out, bool xdp) {
+  BatchLayout l;
+  l.offsets = offsets != nullptr;
+  l.lens = lens != nullptr;
+  l.offsets4 = ((uintptr_t)offsets & 3) == 0;
+  l.lens4 = ((uintptr_t)lens & 3) == 0;
+  l.slots16 = (((uintptr_t)frames | (uintptr_t)stride) & 15) == 0;
+  l.mem_out = mem_out;
+  l.xdp = xdp;
+  l.stride = stride;
+  l.n_tiles = n_tiles;
+  return l;
+}
 
-// The EBPF_KERNEL_* id of the kernel launch_interp runs for (kind, a, jit); stack: a memory
-// tier 0.5 batch.
-int launch_kernel_id(int kind, const LaunchArgs& a, const JitFns* jit, bool stack);
+// Whether a layout is the fixed-slot one (stride layout, 16-byte aligned slots of >= 64 bytes, no
+// lengths, no image output).
+bool launch_fixed_layout(const BatchLayout& l);
+
+// The EBPF_KERNEL_* id of the kernel that runs a batch of layout l: kind and n_uops of the
+// program's table, jit its compiled kernels (null: interpreted), stack: a memory tier 0.5 batch.
+// The one place that decides between the compiled kernels; launch_interp runs the id it is given.
+int launch_kernel_id(int kind, uint32_t n_uops, const BatchLayout& l, const JitFns* jit, bool stack);
 
 // dst[0..7] += src[0..7] on `stream` (one tiny kernel).
 hipError_t launch_counters_add(const uint64_t* src, uint64_t* dst, hipStream_t stream);
 
-// Enqueue the interpreter on `stream`; with counters, its last workgroup folds the shards into them.
-// jit: the program's compiled kernels, launched instead of the tile interpreter where it would run.
-hipError_t launch_interp(int kind, const LaunchArgs& a, int grid, hipStream_t stream,
-                         const JitFns* jit = nullptr, bool stack = false);
+// Enqueue kernel `id` (launch_kernel_id's answer for this batch) on `stream`; with counters, its
+// last workgroup folds the shards into them. jit: the program's compiled kernels (the JIT_* ids).
+// grid: interp_grid's; the compiled kernels size their own from their occupancy.
+hipError_t launch_interp(int id, const LaunchArgs& a, int grid, hipStream_t stream,
+                         const JitFns* jit = nullptr);
 
 }  // namespace ebpfemu

@@ -253,8 +253,10 @@ int ebpf_prog_upload(ebpf_prog* prog, int device);
 int ebpf_run_batch(ebpf_prog* prog, const ebpf_batch* batch, const ebpf_batch_out* out,
                    ebpf_stream_t stream);
 
-/* The kernel ebpf_run_batch would run for this batch and outputs on `device` (uploads the
- * program there first, so it needs that device): one of EBPF_KERNEL_*, or < 0 = EBPF_E*. */
+/* The kernel ebpf_run_batch runs for this batch and outputs on `device`: the kernel id of the
+ * plan ebpf_run_batch executes, made by the same function from the same inputs (host.cpp
+ * plan_batch; the program is uploaded to the device first, so it needs that device). One of
+ * EBPF_KERNEL_*, or < 0 = EBPF_E*. */
 #define EBPF_KERNEL_GENERAL_T0 0  /* interp_kernel, memory tier 0 (read-only packet window) */
 #define EBPF_KERNEL_GENERAL_T1 1  /* interp_kernel, memory tier 1 (per-packet images in scratch) */
 #define EBPF_KERNEL_DAG        2  /* dag_kernel: forward-only programs of 63..256 micro-ops */
@@ -285,7 +287,8 @@ int ebpf_batch_kernel(ebpf_prog* prog, const ebpf_batch* batch, const ebpf_batch
 
 /* Whether ebpf_run_batch stages this EBPF_BATCH_XDP_MD batch's images (one copy kernel writing
  * [ctx][packet] per packet into the workspace before the program's kernel, xdp.rs:16-20) on
- * `device`: 1 staged, 0 in place (or not an xdp_md batch), < 0 = EBPF_E*. */
+ * `device`, read from the same plan as ebpf_batch_kernel's answer: 1 staged, 0 in place (or not
+ * an xdp_md batch), < 0 = EBPF_E*. */
 int ebpf_batch_staged(ebpf_prog* prog, const ebpf_batch* batch, const ebpf_batch_out* out,
                       int device);
 
