@@ -2361,6 +2361,104 @@ int ebpf_pcap_index(const uint8_t* buf, size_t nbytes, uint32_t* offsets, uint16
   return rc;
 }
 
+// ---- verdict queues and the gather (queues.hip) ----
+// Their library-owned scratch per (device, stream): a buffer of its own, [queues region][gather
+// region], so the batch workspace's zeroed counter shards are never touched. Both regions have a
+// fixed size (the grids are capped), so the buffer is allocated once and never grows.
+static std::map<std::pair<int, void*>, void*> g_qws;
+
+static int queues_workspace(void* user, uint64_t user_bytes, uint64_t need, uint64_t lib_off,
+                            int device, hipStream_t s, uint8_t** out) {
+  if (user) {
+    if (user_bytes < need || ((uintptr_t)user & 7)) return EBPF_EINVAL;
+    *out = (uint8_t*)user;
+    return EBPF_OK;
+  }
+  std::lock_guard<std::mutex> lk(g_ws_mu);
+  void*& p = g_qws[{device, (void*)s}];
+  if (!p && hipMalloc(&p, kQWsBytes + kGWsBytes) != hipSuccess) {
+    p = nullptr;
+    return EBPF_ENOMEM;
+  }
+  *out = (uint8_t*)p + lib_off;
+  return EBPF_OK;
+}
+
+static int stream_device(hipStream_t s, int* device) {
+  if (s) return hipStreamGetDevice(s, device) == hipSuccess ? EBPF_OK : EBPF_EHIP;
+  *device = device_of_current();
+  return EBPF_OK;
+}
+
+uint64_t ebpf_queues_workspace_bytes(uint64_t n) {
+  (void)n;  // (the grid is capped: the per-workgroup counts have one size)
+  return kQWsBytes;
+}
+
+int ebpf_verdict_queues(const uint8_t* verdict, uint64_t n, uint32_t* index, uint32_t* count,
+                        void* workspace, uint64_t workspace_bytes, ebpf_stream_t stream) {
+  static_assert(kQClasses == EBPF_NQUEUES, "include/ebpf_emu.h names the number of queues");
+  if (n > 0xFFFFFFFFull) return EBPF_ETOOBIG;
+  if (!count || (n && (!verdict || !index))) return EBPF_EINVAL;
+  if (workspace && (workspace_bytes < kQWsBytes || ((uintptr_t)workspace & 7))) return EBPF_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  int device = 0;
+  int rc = stream_device(s, &device);
+  if (rc) return rc;
+  DeviceScope on(device);
+  if (n == 0)
+    return hipMemsetAsync(count, 0, EBPF_NQUEUES * sizeof(uint32_t), s) == hipSuccess ? EBPF_OK
+                                                                                      : EBPF_EHIP;
+  uint8_t* ws = nullptr;
+  rc = queues_workspace(workspace, workspace_bytes, kQWsBytes, 0, device, s, &ws);
+  if (rc) return rc;
+  return launch_queues(verdict, n, index, count, ws, s) == hipSuccess ? EBPF_OK : EBPF_EHIP;
+}
+
+uint64_t ebpf_gather_workspace_bytes(uint64_t n) {
+  (void)n;
+  return kGWsBytes;
+}
+
+int ebpf_gather(const ebpf_gather_desc* g, ebpf_stream_t stream) {
+  if (!g) return EBPF_EINVAL;
+  if (!g->index || !g->count || !g->out_offsets || !g->out_lens || !g->out_total) return EBPF_EINVAL;
+  if ((g->n && !g->frames) || (g->out_bytes && !g->out_frames)) return EBPF_EINVAL;
+  if (!g->offsets && g->stride == 0 && !g->lens) return EBPF_EINVAL;  // no packet layout
+  if (!g->lens && g->stride > 0xFFFF) return EBPF_EINVAL;             // (out_lens are u16)
+  if (g->queue >= EBPF_NQUEUES) return EBPF_EINVAL;
+  if (g->align == 0 || g->align > 256 || (g->align & (g->align - 1))) return EBPF_EINVAL;
+  if (g->n > 0xFFFFFFFFull || g->out_bytes > (1ull << 32)) return EBPF_ETOOBIG;
+  if (g->workspace && (g->workspace_bytes < kGWsBytes || ((uintptr_t)g->workspace & 7)))
+    return EBPF_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  int device = 0;
+  int rc = stream_device(s, &device);
+  if (rc) return rc;
+  DeviceScope on(device);
+  uint8_t* ws = nullptr;
+  rc = queues_workspace(g->workspace, g->workspace_bytes, kGWsBytes, kQWsBytes, device, s, &ws);
+  if (rc) return rc;
+  GatherArgs a{};
+  a.frames = g->frames;
+  a.offsets = g->offsets;
+  a.lens = g->lens;
+  a.stride = g->stride;
+  a.n = g->n;
+  a.index = g->index;
+  a.count = g->count;
+  a.queue = g->queue;
+  a.align = g->align;
+  a.out_frames = g->out_frames;
+  // (offsets and the end byte are u32: a packet is written only if it ends at or below 2^32 - 1)
+  a.cap = std::min<uint64_t>(g->out_bytes, 0xFFFFFFFFull);
+  a.out_offsets = g->out_offsets;
+  a.out_lens = g->out_lens;
+  a.out_total = g->out_total;
+  a.wsum = (unsigned long long*)ws;
+  return launch_gather(a, s) == hipSuccess ? EBPF_OK : EBPF_EHIP;
+}
+
 const char* ebpf_strerror(int err) {
   switch (err) {
     case EBPF_OK: return "ok";

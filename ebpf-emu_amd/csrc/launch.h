@@ -192,4 +192,45 @@ hipError_t launch_counters_add(const uint64_t* src, uint64_t* dst, hipStream_t s
 hipError_t launch_interp(int id, const LaunchArgs& a, int grid, hipStream_t stream,
                          const JitFns* jit = nullptr);
 
+// ---- verdict queues and the packet gather (queues.hip) ----
+constexpr int kQBlock = 256;             // 4 waves per workgroup
+constexpr int kQWaves = kQBlock / kWave;
+constexpr int kQClasses = 7;             // EBPF_NQUEUES
+constexpr int kQSlots = 8;               // counts are kept 8 to a row (slot 7 is zero)
+constexpr uint32_t kQRange = 4096;       // a workgroup's packets: a whole number of these, one
+                                         // while the grid is not capped (each wave a quarter)
+constexpr int kQMaxWgs = 1024;           // queues grid cap (a larger batch: longer ranges)
+constexpr uint32_t kGTile = 256;         // gather: queue positions per workgroup pass (one a thread)
+constexpr int kGMaxWgs = 1024;           // gather grid cap (a longer queue: several tiles in order)
+// workspaces: [workgroup counts u32[kQMaxWgs][8]][wave counts u32[kQMaxWgs][4][8]]; the gather's
+// workgroup byte sums u64[kGMaxWgs]. Neither needs zeroing: every word read was written first.
+constexpr uint64_t kQWsWaveOff = (uint64_t)kQMaxWgs * kQSlots * 4;
+constexpr uint64_t kQWsBytes = kQWsWaveOff + (uint64_t)kQMaxWgs * kQWaves * kQSlots * 4;
+constexpr uint64_t kGWsBytes = (uint64_t)kGMaxWgs * 8;
+
+// index[n] = the packet numbers stably partitioned by verdict class, count[7] = the class sizes
+// (include/ebpf_emu.h ebpf_verdict_queues). Two kernels on `stream`; n >= 1.
+hipError_t launch_queues(const uint8_t* verdict, uint64_t n, uint32_t* index, uint32_t* count,
+                         uint8_t* ws, hipStream_t stream);
+
+struct GatherArgs {  // ebpf_gather_desc, checked (cap = min(out_bytes, 2^32 - 1))
+  const uint8_t* frames;
+  const uint32_t* offsets;
+  const uint16_t* lens;
+  uint64_t stride;
+  uint64_t n;
+  const uint32_t* index;
+  const uint32_t* count;
+  uint32_t queue;
+  uint32_t align;
+  uint8_t* out_frames;
+  uint64_t cap;
+  uint32_t* out_offsets;
+  uint16_t* out_lens;
+  uint32_t* out_total;
+  unsigned long long* wsum;  // workspace: u64[grid]
+};
+// Two kernels on `stream` (include/ebpf_emu.h ebpf_gather).
+hipError_t launch_gather(const GatherArgs& g, hipStream_t stream);
+
 }  // namespace ebpfemu

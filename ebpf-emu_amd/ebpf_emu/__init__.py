@@ -16,6 +16,10 @@ def __getattr__(name):  # lazy: these import torch
         from . import program
 
         return getattr(program, name)
+    if name in ("verdict_queues", "gather", "GatherResult"):
+        from . import queues
+
+        return getattr(queues, name)
     if name in ("Emu", "EmuPanic"):
         from . import emu
 

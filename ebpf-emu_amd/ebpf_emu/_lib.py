@@ -29,6 +29,7 @@ BATCH_XDP_MD = 2   # ebpf_batch.flags: EBPF_BATCH_XDP_MD (the xdp_md calling con
 BATCH_NO_JIT = 4   # ebpf_batch.flags: EBPF_BATCH_NO_JIT (the tile interpreter, not the compiled program)
 BATCH_WRITEBACK = 8  # ebpf_batch.flags: EBPF_BATCH_WRITEBACK (rewritten packets written back in place)
 MAX_CALL_DEPTH = 64
+NQUEUES = 7  # EBPF_NQUEUES: queue q = verdict q for q < 5, 5 = other bytes, 6 = EBPF_VERDICT_FAULT
 # ebpf_batch_kernel ids (EBPF_KERNEL_*)
 (EBPF_KERNEL_GENERAL_T0, EBPF_KERNEL_GENERAL_T1, EBPF_KERNEL_DAG, EBPF_KERNEL_TILE,
  EBPF_KERNEL_TILE_LOOP, EBPF_KERNEL_JIT_FIXED, EBPF_KERNEL_JIT_VAR, EBPF_KERNEL_JIT_LOOP,
@@ -51,6 +52,8 @@ EXPORTS = ["ebpf_batch_init", "ebpf_prog_load", "ebpf_prog_load_hex", "ebpf_prog
            "ebpf_workspace_bytes", "ebpf_prog_compile", "ebpf_prog_jit_asm", "ebpf_prog_jit_error", "ebpf_debug_trace",
            "ebpf_prog_upload", "ebpf_run_batch", "ebpf_run_batch_multi", "ebpf_batch_kernel", "ebpf_batch_staged",
            "ebpf_pcap_index",
+           "ebpf_queues_workspace_bytes", "ebpf_verdict_queues", "ebpf_gather_workspace_bytes",
+           "ebpf_gather",
            "ebpf_strerror", "ebpf_version"]
 
 
@@ -68,6 +71,17 @@ class BatchOut(ctypes.Structure):  # ebpf_batch_out
     _fields_ = [("verdict", ctypes.c_void_p), ("r0", ctypes.c_void_p), ("status", ctypes.c_void_p),
                 ("counters", ctypes.c_void_p), ("mem", ctypes.c_void_p), ("regs", ctypes.c_void_p),
                 ("fp", ctypes.c_void_p), ("fp_len", ctypes.c_void_p)]
+
+
+class GatherDesc(ctypes.Structure):  # ebpf_gather_desc
+    _fields_ = [("frames", ctypes.c_void_p), ("offsets", ctypes.c_void_p),
+                ("lens", ctypes.c_void_p), ("stride", ctypes.c_uint64), ("n", ctypes.c_uint64),
+                ("index", ctypes.c_void_p), ("count", ctypes.c_void_p),
+                ("queue", ctypes.c_uint32), ("align", ctypes.c_uint32),
+                ("out_frames", ctypes.c_void_p), ("out_bytes", ctypes.c_uint64),
+                ("out_offsets", ctypes.c_void_p), ("out_lens", ctypes.c_void_p),
+                ("out_total", ctypes.c_void_p),
+                ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_uint64)]
 
 
 class EbpfError(RuntimeError):
@@ -131,6 +145,15 @@ def lib():
                                        ctypes.POINTER(vp)]
     L.ebpf_pcap_index.argtypes = [vp, sz, vp, vp, sz, ctypes.POINTER(sz),
                                   ctypes.POINTER(ctypes.c_uint32)]
+    # (an EBPFEMU_LIB_PATH build from before the queues still loads for the A/B runs of the batch
+    # path; a queues call on it raises AttributeError -- nothing stands in for a missing symbol)
+    if hasattr(L, "ebpf_verdict_queues"):
+        L.ebpf_queues_workspace_bytes.argtypes = [u64]
+        L.ebpf_queues_workspace_bytes.restype = u64
+        L.ebpf_verdict_queues.argtypes = [vp, u64, vp, vp, vp, u64, vp]
+        L.ebpf_gather_workspace_bytes.argtypes = [u64]
+        L.ebpf_gather_workspace_bytes.restype = u64
+        L.ebpf_gather.argtypes = [ctypes.POINTER(GatherDesc), vp]
     L.ebpf_strerror.argtypes = [ctypes.c_int]
     L.ebpf_strerror.restype = ctypes.c_char_p
     L.ebpf_version.restype = ctypes.c_char_p

@@ -25,6 +25,8 @@ class BatchResult:
     regs: object = None      # torch.int64 [n, 11]
     fp: object = None        # torch.int32 [n, 64] (u32 bits): final frame stacks, bottom first
     fp_len: object = None    # torch.uint8 [n]: their depths
+    queue_index: object = None  # torch.int32 [n] (u32 bits): run(queues=True), queues.verdict_queues
+    queue_count: object = None  # torch.int32 [7]: the queues' sizes (queue q starts at count[:q].sum())
 
 
 def _ptr(t):
@@ -244,7 +246,7 @@ class Program:
             r0: bool = False, status: bool = False, counters=None, mem: bool = False,
             regs: bool = False, stream=None, generic: bool = False,
             xdp_md: bool = False, no_jit: bool = False, init_fp=None,
-            fp: bool = False, writeback: bool = False) -> BatchResult:
+            fp: bool = False, writeback: bool = False, queues: bool = False) -> BatchResult:
         """Run the program over a device-resident batch; returns device tensors.
 
         frames: torch.uint8 CUDA tensor. Layout: packet i at frames[i*stride:] (stride layout,
@@ -260,9 +262,13 @@ class Program:
         its rewritten bytes [0, len) once the batch has completed on its stream, every other
         packet and every byte outside the packets is untouched. Packets must not overlap; frames
         must be a writable, contiguous tensor.
+        queues: also partition the packet numbers by verdict on the same stream
+        (ebpf_verdict_queues: res.queue_index, res.queue_count); requires verdict=True.
         """
         import torch
 
+        if queues and not verdict:
+            raise ValueError("queues=True partitions the verdicts: it requires verdict=True")
         dev = frames.device
         if writeback:
             if not frames.is_contiguous():
@@ -300,6 +306,10 @@ class Program:
         out.fp_len = res.fp_len.data_ptr() if fp else None
         with torch.cuda.device(dev):
             self.launch(b, out, stream)
+        if queues:
+            from .queues import verdict_queues
+
+            res.queue_index, res.queue_count = verdict_queues(res.verdict, stream)
         return res
 
 

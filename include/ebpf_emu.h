@@ -317,6 +317,74 @@ int ebpf_run_batch_multi(ebpf_prog* prog, int nshards, const int* devices,
 int ebpf_pcap_index(const uint8_t* buf, size_t nbytes, uint32_t* offsets, uint16_t* lens,
                     size_t cap, size_t* n, uint32_t* linktype);
 
+/* ---- verdict queues and the packet gather: what a datapath does with a batch's verdicts ----
+ * (new: no reference counterpart; the reference runs one packet and prints r0. The queues follow
+ * the action enum, xdp.rs:3-9.) Both calls are asynchronous and ordered on `stream` as
+ * ebpf_run_batch is, make no host synchronisation, and allocate nothing when a workspace is
+ * passed: run -> queues -> gather -> run chains on one stream with no host round trip. */
+
+/* Queue q holds the packets of verdict q for q = 0..4 (ABORTED, DROP, PASS, TX, REDIRECT);
+ * queue 5 every other verdict byte but 0xFF (EBPF_VERDICT_OTHER; bytes 5..0xFD count here too);
+ * queue 6 EBPF_VERDICT_FAULT -- the order of counters 0..6. */
+#define EBPF_NQUEUES 7
+
+/* Device scratch ebpf_verdict_queues needs for n packets (8-byte aligned; needs no zeroing). */
+uint64_t ebpf_queues_workspace_bytes(uint64_t n);
+
+/* The stable partition of the packet numbers 0..n-1 by queue. Once complete on the stream:
+ * count[q] = packets in queue q; queue q is index[start_q .. start_q + count[q]) with start_q =
+ * count[0] + ... + count[q-1]; inside a queue the packet numbers ascend (a flow's packets leave in
+ * arrival order; the result is deterministic).
+ * verdict: device u8[n] (any alignment); index: device u32[n]; count: device u32[EBPF_NQUEUES],
+ * OVERWRITTEN. workspace: device scratch of ebpf_queues_workspace_bytes(n) bytes, one per stream;
+ * NULL => library-owned per (device, stream), a buffer of its own (not the batch workspace).
+ * n == 0 is valid: the counts are 0 and nothing else is written. Returns EBPF_ETOOBIG for
+ * n > UINT32_MAX; EBPF_EINVAL, before any device call, for a NULL count, a NULL verdict or index
+ * with n > 0, or a workspace that is too small. */
+int ebpf_verdict_queues(const uint8_t* verdict, uint64_t n, uint32_t* index, uint32_t* count,
+                        void* workspace, uint64_t workspace_bytes, ebpf_stream_t stream);
+
+/* One queue's packets copied into a dense offsets + lens batch (itself the input of a next
+ * ebpf_run_batch: out_frames / out_offsets / out_lens with n = out_total[0]). All pointers are
+ * DEVICE pointers. */
+typedef struct ebpf_gather_desc {
+  const uint8_t* frames;    /* the source batch, as in ebpf_batch: packet i at frames + offsets[i], */
+  const uint32_t* offsets;  /*   or frames + i*stride when NULL; */
+  const uint16_t* lens;     /*   its length lens[i], or stride when NULL (then stride <= 65535) */
+  uint64_t stride;
+  uint64_t n;               /* packets in the source batch (<= UINT32_MAX) */
+  const uint32_t* index;    /* ebpf_verdict_queues' index, u32[n] */
+  const uint32_t* count;    /* its count[EBPF_NQUEUES], READ ON THE DEVICE (no host sync) */
+  uint32_t queue;           /* 0..EBPF_NQUEUES-1 */
+  uint32_t align;           /* power of two, 1..256: output packet j starts at a multiple of it */
+  uint8_t* out_frames;      /* u8[out_bytes] */
+  uint64_t out_bytes;       /* <= 4 GiB (u32 offsets) */
+  uint32_t* out_offsets;    /* u32[n] */
+  uint16_t* out_lens;       /* u16[n] */
+  uint32_t* out_total;      /* u32[2], OVERWRITTEN: packets written, end byte of the last one */
+  void* workspace;          /* optional scratch of ebpf_gather_workspace_bytes(n) bytes (8-byte
+                               aligned, no zeroing); NULL => library-owned per (device, stream) */
+  uint64_t workspace_bytes;
+} ebpf_gather_desc;
+
+uint64_t ebpf_gather_workspace_bytes(uint64_t n);
+
+/* With m = count[queue] and s_j the j-th packet of that queue: out_lens[j] = len(s_j);
+ * out_offsets[j] = the sum over i < j of alignup(len(s_i), align); out_frames[out_offsets[j] ..
+ * + len) = the packet's bytes as they are in `frames` when the call runs on the stream (after an
+ * EBPF_BATCH_WRITEBACK batch: the rewritten bytes). A zero-length packet gets an entry and no
+ * bytes. Packet j is written iff out_offsets[j] + len <= out_bytes (and <= 2^32 - 1: the offsets
+ * and the end byte are u32); the offsets ascend, so the written packets are a prefix, and
+ * out_total = {packets written, out_offsets[last] + len(last)} ({0, 0} when none). Entries of
+ * out_offsets / out_lens at or past the prefix, every byte at or past out_bytes and every byte at
+ * or past alignup(out_total[1], align) are untouched; the padding between a packet's end and the
+ * next multiple of align has unspecified content. Source and output must not overlap (not
+ * checked). The grid is sized from n and m is read on the device. Returns EBPF_EINVAL, before any
+ * device call, for a NULL descriptor or pointer (out_frames may be NULL with out_bytes 0), no
+ * packet layout, queue >= EBPF_NQUEUES, align not a power of two in 1..256 or a workspace that is
+ * too small; EBPF_ETOOBIG for out_bytes > 4 GiB or n > UINT32_MAX. */
+int ebpf_gather(const ebpf_gather_desc* g, ebpf_stream_t stream);
+
 /* Human-readable message for an EBPF_E* code. */
 const char* ebpf_strerror(int err);
 
