@@ -2459,6 +2459,48 @@ int ebpf_gather(const ebpf_gather_desc* g, ebpf_stream_t stream) {
   return launch_gather(a, s) == hipSuccess ? EBPF_OK : EBPF_EHIP;
 }
 
+uint64_t ebpf_scatter_workspace_bytes(uint64_t cap) {
+  (void)cap;  // (destinations and source offsets are both given: no scratch)
+  return 0;
+}
+
+int ebpf_scatter(const ebpf_scatter_desc* d, ebpf_stream_t stream) {
+  if (!d) return EBPF_EINVAL;
+  if (!d->index || !d->count || d->queue >= EBPF_NQUEUES) return EBPF_EINVAL;
+  if (d->frames && (!d->src_frames || !d->src_offsets || !d->src_lens)) return EBPF_EINVAL;
+  if (d->frames && !d->offsets && d->stride == 0) return EBPF_EINVAL;  // no packet layout
+  if (d->workspace && d->workspace_bytes < ebpf_scatter_workspace_bytes(d->cap)) return EBPF_EINVAL;
+  if (d->n > 0xFFFFFFFFull || d->cap > 0xFFFFFFFFull || d->src_bytes > (1ull << 32))
+    return EBPF_ETOOBIG;
+  ScatterArgs a{};
+  a.index = d->index;
+  a.count = d->count;
+  a.total = d->total;
+  a.queue = d->queue;
+  a.cap = (uint32_t)d->cap;
+  a.src_frames = d->src_frames;
+  a.src_bytes = d->src_bytes;
+  a.src_offsets = d->src_offsets;
+  a.src_lens = d->src_lens;
+  a.frames = d->frames;
+  a.offsets = d->offsets;
+  a.lens = d->lens;
+  a.stride = d->stride;
+  a.n = d->n;
+  // a result array is written only when it and its src_ partner are both present
+  if (d->verdict && d->src_verdict) a.verdict = d->verdict, a.src_verdict = d->src_verdict;
+  if (d->status && d->src_status) a.status = d->status, a.src_status = d->src_status;
+  if (d->r0 && d->src_r0) a.r0 = d->r0, a.src_r0 = d->src_r0;
+  // nothing to scatter, nothing to write: valid, and no launch
+  if (a.cap == 0 || a.n == 0 || (!a.frames && !a.verdict && !a.status && !a.r0)) return EBPF_OK;
+  hipStream_t s = (hipStream_t)stream;
+  int device = 0;
+  int rc = stream_device(s, &device);
+  if (rc) return rc;
+  DeviceScope on(device);
+  return launch_scatter(a, s) == hipSuccess ? EBPF_OK : EBPF_EHIP;
+}
+
 const char* ebpf_strerror(int err) {
   switch (err) {
     case EBPF_OK: return "ok";

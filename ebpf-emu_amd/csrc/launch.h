@@ -233,4 +233,31 @@ struct GatherArgs {  // ebpf_gather_desc, checked (cap = min(out_bytes, 2^32 - 1
 // Two kernels on `stream` (include/ebpf_emu.h ebpf_gather).
 hipError_t launch_gather(const GatherArgs& g, hipStream_t stream);
 
+// ---- the scatter: a gathered queue's packets and results put back (queues.hip)
+struct ScatterArgs {  // ebpf_scatter_desc, checked: a result pair is both set or both null, the
+                      // src_ packet arrays are set with frames, cap >= 1
+  const uint32_t* index;
+  const uint32_t* count;
+  const uint32_t* total;
+  uint32_t queue;
+  uint32_t cap;
+  const uint8_t* src_frames;
+  uint64_t src_bytes;
+  const uint32_t* src_offsets;
+  const uint16_t* src_lens;
+  const uint8_t* src_verdict;
+  const uint8_t* src_status;
+  const uint64_t* src_r0;
+  uint8_t* frames;
+  const uint32_t* offsets;
+  const uint16_t* lens;
+  uint64_t stride;
+  uint64_t n;
+  uint8_t* verdict;
+  uint8_t* status;
+  uint64_t* r0;
+};
+// One kernel on `stream`, its grid sized from cap as the gather's is from n (kGTile, kGMaxWgs).
+hipError_t launch_scatter(const ScatterArgs& s, hipStream_t stream);
+
 }  // namespace ebpfemu

@@ -1,9 +1,11 @@
 // queues.hip — what a datapath does with a batch's verdicts: the stable
 // partition of the packet numbers by XDP action (ebpf_verdict_queues) and the copy of one queue's
-// packets into a dense offsets + lens batch (ebpf_gather). New: no reference counterpart (the
-// reference runs one packet and prints r0); xdp.rs:3-9 is the action enum the queues follow.
+// packets into a dense offsets + lens batch (ebpf_gather), and the way back (§3.39): that dense
+// batch's packets and results put back at the packets' own numbers (ebpf_scatter, one launch).
+// New: no reference counterpart (the reference runs one packet and prints r0); xdp.rs:3-9 is the
+// action enum the queues follow.
 //
-// Both are count -> bases -> write over contiguous per-workgroup ranges, in separate launches:
+// The first two are count -> bases -> write over contiguous per-workgroup ranges, in separate launches:
 // the launch boundary is the only ordering between workgroups. No workgroup ever waits on
 // another one's progress (no look-back, no flag, no grid barrier, no cooperative launch), so a
 // grid larger than the resident set cannot hang. No device atomics; the only LDS atomics add up
@@ -179,18 +181,19 @@ __device__ __forceinline__ u32x4 blk16(uintptr_t a, uintptr_t src, uintptr_t end
   return *(g_u4*)a;
 }
 
-// Packet bytes [16 c, 16 c + 16) of a packet of len bytes at src, 16 c < len < 16 c + 16 (its
-// last, partial chunk): the two aligned 16-byte blocks that hold them, each read only where it
-// holds a byte of the packet, funnel-shifted (v_alignbyte); bytes at or past len are zero.
-__device__ __forceinline__ u32x4 tail_chunk(const uint8_t* src, uint32_t len, uint32_t c) {
+// Packet bytes [off, off + rem) of a packet of len bytes at src, 1 <= rem <= 15 and off + rem <=
+// len (a partial chunk), in the result's low bytes: the two aligned 16-byte blocks that hold them,
+// each read only where it holds a byte of the packet, funnel-shifted (v_alignbyte); the bytes at
+// or past rem are zero.
+__device__ __forceinline__ u32x4 span_load(const uint8_t* src, uint32_t len, uint32_t off,
+                                           uint32_t rem) {
   const uintptr_t s0 = (uintptr_t)src, end = s0 + len;
-  const uintptr_t p = s0 + 16ull * c;
+  const uintptr_t p = s0 + off;
   const uintptr_t a0 = p & ~(uintptr_t)15;
   const uint32_t sh = (uint32_t)(p & 15), q = sh >> 2;
   const u32x4 b0 = blk16(a0, s0, end);
   const u32x4 b1 = sh ? blk16(a0 + 16, s0, end) : u32x4{0u, 0u, 0u, 0u};
   const uint32_t d[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-  const uint32_t rem = len - 16 * c;
   uint32_t w[4];
 #pragma unroll
   for (int k = 0; k < 4; k++) {
@@ -204,6 +207,11 @@ __device__ __forceinline__ u32x4 tail_chunk(const uint8_t* src, uint32_t len, ui
     w[k] = valid >= 4 ? v : v & ((1u << (8 * valid)) - 1u);
   }
   return u32x4{w[0], w[1], w[2], w[3]};
+}
+
+// A packet's last, partial chunk: its bytes [16 c, len), 16 c < len < 16 c + 16.
+__device__ __forceinline__ u32x4 tail_chunk(const uint8_t* src, uint32_t len, uint32_t c) {
+  return span_load(src, len, 16 * c, len - 16 * c);
 }
 
 // The first rem (1..15) bytes of v to dst, no byte more: 8 + 4 + 2 + 1.
@@ -403,6 +411,195 @@ __global__ __launch_bounds__(kGTile) void gather_copy(GatherArgs a) {
   }
 }
 
+// ============================================================================================
+// Scatter: the gather reversed. Queue position j's destination (packet
+// index[start + j] of the original batch) and its source (src_offsets[j] of the dense buffer) are
+// both given, so there is no prefix across workgroups and one launch does it: the m positions are
+// split into contiguous per-workgroup ranges of whole kGTile tiles as the gather's are; a thread
+// per position merges the entry's results and works out its packet's copy, then the tile's chunks
+// are dealt to the lanes as gather_copy deals its. The chunks are cut on the DESTINATION's
+// 16-byte grid: chunk c of a packet at address D is the part of the aligned block (D & ~15) +
+// 16 c that holds its bytes, so an inside chunk is one unaligned 16-byte load and one aligned
+// 16-byte store, and only a packet's first and last chunk are partial. Other lanes (and other
+// workgroups) write the bytes next to a partial chunk at the same time, so it is stored with
+// naturally aligned 1/2/4/8-byte stores of exactly its bytes, never by a read-modify-write.
+// ============================================================================================
+typedef __attribute__((address_space(1))) u32x4 gs_u4;
+typedef __attribute__((address_space(1))) uint64_t gs_u64;
+typedef __attribute__((address_space(1))) uint32_t gs_u32;
+typedef __attribute__((address_space(1))) uint16_t gs_u16;
+typedef __attribute__((address_space(1))) uint8_t gs_u8;
+
+// The first cnt (1..15) bytes of v to the address p, no byte more, p + cnt inside p's aligned
+// 16-byte block: 1, 2, 4, 8 bytes while p's alignment asks for them and they fit, then 8, 4, 2, 1
+// of what is left -- every store naturally aligned.
+__device__ __forceinline__ void store_span(uintptr_t p, u32x4 v, uint32_t cnt) {
+  uint64_t lo = (uint64_t)v.x | ((uint64_t)v.y << 32);
+  uint64_t hi = (uint64_t)v.z | ((uint64_t)v.w << 32);
+  if ((p & 1) && cnt >= 1) {
+    *(gs_u8*)p = (uint8_t)lo;
+    lo = (lo >> 8) | (hi << 56);
+    hi >>= 8;
+    p += 1, cnt -= 1;
+  }
+  if ((p & 2) && cnt >= 2) {
+    *(gs_u16*)p = (uint16_t)lo;
+    lo = (lo >> 16) | (hi << 48);
+    hi >>= 16;
+    p += 2, cnt -= 2;
+  }
+  if ((p & 4) && cnt >= 4) {
+    *(gs_u32*)p = (uint32_t)lo;
+    lo = (lo >> 32) | (hi << 32);
+    hi >>= 32;
+    p += 4, cnt -= 4;
+  }
+  if ((p & 8) && cnt >= 8) {
+    *(gs_u64*)p = lo;
+    lo = hi;
+    p += 8, cnt -= 8;
+  }
+  // (a step skipped for room leaves p aligned to its size and fewer bytes than it: the stores
+  // below, of cnt's bits from the highest down, are aligned too; else p is 16-byte aligned)
+  if (cnt & 8) {
+    *(gs_u64*)p = lo;
+    lo = hi;
+    p += 8;
+  }
+  if (cnt & 4) {
+    *(gs_u32*)p = (uint32_t)lo;
+    lo >>= 32;
+    p += 4;
+  }
+  if (cnt & 2) {
+    *(gs_u16*)p = (uint16_t)lo;
+    lo >>= 16;
+    p += 2;
+  }
+  if (cnt & 1) *(gs_u8*)p = (uint8_t)lo;
+}
+
+struct SQueue {
+  uint32_t start, m;  // the positions scattered are index[start .. start + m)
+  uint64_t span;      // queue positions per workgroup
+};
+__device__ __forceinline__ SQueue s_queue(const ScatterArgs& a, uint32_t grid) {
+  uint64_t start = 0;
+  for (uint32_t c = 0; c < a.queue; c++) start += a.count[c];
+  uint64_t m = a.count[a.queue];
+  // (counts that do not belong to this batch: stay inside index[0, n))
+  if (start > a.n) start = a.n;
+  if (m > a.n - start) m = a.n - start;
+  if (m > a.cap) m = a.cap;
+  if (a.total && m > a.total[0]) m = a.total[0];
+  SQueue q;
+  q.start = (uint32_t)start;
+  q.m = (uint32_t)m;
+  const uint64_t per = (m + grid - 1) / grid;
+  q.span = (per + kGTile - 1) / kGTile * kGTile;
+  return q;
+}
+
+__global__ __launch_bounds__(kGTile) void scatter_copy(ScatterArgs a) {
+  __shared__ uint32_t cpre[kGTile], len_s[kGTile];
+  __shared__ const uint8_t* src_s[kGTile];
+  __shared__ uintptr_t dst_s[kGTile];
+  const uint32_t t = threadIdx.x, g = blockIdx.x;
+  const SQueue q = s_queue(a, gridDim.x);
+  const uint64_t beg = (uint64_t)g * q.span;
+  const uint64_t end = beg + q.span < q.m ? beg + q.span : q.m;
+  for (uint64_t tb = beg; tb < end; tb += kGTile) {  // (uniform)
+    const uint64_t j = tb + t;
+    uint32_t L = 0;  // bytes of this position's packet to copy
+    const uint8_t* S = a.src_frames;
+    uintptr_t D = (uintptr_t)a.frames;
+    if (j < end) {
+      const uint64_t d = a.index[q.start + j];
+      bool ok = d < a.n;
+      if (ok && a.frames) {
+        const uint64_t so = a.src_offsets[j];
+        const uint32_t sl = a.src_lens[j];
+        ok = so + sl <= a.src_bytes;
+        if (ok) {
+          const uint64_t dl = a.lens ? (uint64_t)a.lens[d] : a.stride;
+          L = dl < sl ? (uint32_t)dl : sl;
+          S = a.src_frames + so;
+          D = (uintptr_t)a.frames + (a.offsets ? (uint64_t)a.offsets[d] : d * a.stride);
+        }
+      }
+      if (ok) {  // a wrong index, a source span past the dense buffer: no results either
+        if (a.verdict) a.verdict[d] = a.src_verdict[j];
+        if (a.status) a.status[d] = a.src_status[j];
+        if (a.r0) a.r0[d] = a.src_r0[j];
+      }
+    }
+    if (!a.frames) continue;  // (uniform) results only
+    len_s[t] = L;
+    src_s[t] = S;
+    dst_s[t] = D;
+    // the aligned 16-byte blocks that hold a byte of [D, D + L)
+    cpre[t] = L ? (uint32_t)(((D + L + 15) >> 4) - (D >> 4)) : 0u;
+    __syncthreads();
+    for (uint32_t d = 1; d < kGTile; d <<= 1) {  // inclusive scan of the chunk counts
+      const uint32_t v = t >= d ? cpre[t - d] : 0u;
+      __syncthreads();
+      cpre[t] += v;
+      __syncthreads();
+    }
+    // wave w copies the w-th quarter of the tile's chunks, lane l the chunks l, l + 64, ... of it,
+    // four in flight before any store (gather_copy's deal)
+    const uint32_t chunks = cpre[kGTile - 1];
+    const uint32_t wv = t >> 6, ln = t & 63, qc = (chunks + 3) / 4;
+    const uint32_t kb = min(wv * qc, chunks), ke = min(kb + qc, chunks);
+    uint32_t p = 0;
+    if (kb + ln < ke) {
+      uint32_t lo = 0, hi = kGTile - 1;  // (cpre[kGTile - 1] > k for every k < chunks)
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (cpre[mid] <= kb + ln) lo = mid + 1;
+        else hi = mid;
+      }
+      p = lo;
+    }
+    for (uint32_t k0 = kb + ln; k0 < ke; k0 += 4 * 64) {
+      u32x4 v[4];
+      uintptr_t at[4];
+      uint32_t cnt[4];  // 0: nothing, 16: the whole aligned block, else that many bytes at at[u]
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const uint32_t k = k0 + 64 * u;
+        cnt[u] = 0;
+        at[u] = 0;
+        v[u] = u32x4{0u, 0u, 0u, 0u};
+        if (k >= ke) continue;
+        while (cpre[p] <= k) p++;
+        const uint32_t c = k - (p ? cpre[p - 1] : 0u);
+        const uint32_t lp = len_s[p];
+        const uint8_t* sp = src_s[p];
+        const uintptr_t dp = dst_s[p];
+        const uintptr_t blk = (dp & ~(uintptr_t)15) + 16ull * c;
+        const uintptr_t lo = blk > dp ? blk : dp;
+        const uintptr_t hi = blk + 16 < dp + lp ? blk + 16 : dp + lp;
+        const uint32_t off = (uint32_t)(lo - dp);  // the chunk's first byte inside the packet
+        at[u] = lo;
+        cnt[u] = (uint32_t)(hi - lo);
+        if (cnt[u] == 16) {  // inside the packet: one load, as it lies
+          const u32x4_any x = *(g_u4_any*)((uintptr_t)sp + off);
+          v[u] = u32x4{x.x, x.y, x.z, x.w};
+        } else {
+          v[u] = span_load(sp, lp, off, cnt[u]);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        if (cnt[u] == 16) *(gs_u4*)at[u] = v[u];
+        else if (cnt[u]) store_span(at[u], v[u], cnt[u]);
+      }
+    }
+    __syncthreads();  // (the next tile rewrites the LDS arrays)
+  }
+}
+
 }  // namespace
 
 hipError_t launch_queues(const uint8_t* verdict, uint64_t n, uint32_t* index, uint32_t* count,
@@ -422,6 +619,13 @@ hipError_t launch_gather(const GatherArgs& a, hipStream_t stream) {
   const int grid = (int)(g < 1 ? 1 : g > (uint64_t)kGMaxWgs ? (uint64_t)kGMaxWgs : g);
   hipLaunchKernelGGL(gather_sums, dim3(grid), dim3(kGTile), 0, stream, a);
   hipLaunchKernelGGL(gather_copy, dim3(grid), dim3(kGTile), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_scatter(const ScatterArgs& a, hipStream_t stream) {
+  const uint64_t g = ((uint64_t)a.cap + kGTile - 1) / kGTile;
+  const int grid = (int)(g < 1 ? 1 : g > (uint64_t)kGMaxWgs ? (uint64_t)kGMaxWgs : g);
+  hipLaunchKernelGGL(scatter_copy, dim3(grid), dim3(kGTile), 0, stream, a);
   return hipGetLastError();
 }
 

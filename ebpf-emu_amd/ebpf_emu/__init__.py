@@ -16,7 +16,8 @@ def __getattr__(name):  # lazy: these import torch
         from . import program
 
         return getattr(program, name)
-    if name in ("verdict_queues", "gather", "GatherResult"):
+    if name in ("verdict_queues", "gather", "GatherResult", "scatter", "two_stage",
+                "TwoStageResult"):
         from . import queues
 
         return getattr(queues, name)

@@ -53,7 +53,7 @@ EXPORTS = ["ebpf_batch_init", "ebpf_prog_load", "ebpf_prog_load_hex", "ebpf_prog
            "ebpf_prog_upload", "ebpf_run_batch", "ebpf_run_batch_multi", "ebpf_batch_kernel", "ebpf_batch_staged",
            "ebpf_pcap_index",
            "ebpf_queues_workspace_bytes", "ebpf_verdict_queues", "ebpf_gather_workspace_bytes",
-           "ebpf_gather",
+           "ebpf_gather", "ebpf_scatter_workspace_bytes", "ebpf_scatter",
            "ebpf_strerror", "ebpf_version"]
 
 
@@ -81,6 +81,19 @@ class GatherDesc(ctypes.Structure):  # ebpf_gather_desc
                 ("out_frames", ctypes.c_void_p), ("out_bytes", ctypes.c_uint64),
                 ("out_offsets", ctypes.c_void_p), ("out_lens", ctypes.c_void_p),
                 ("out_total", ctypes.c_void_p),
+                ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_uint64)]
+
+
+class ScatterDesc(ctypes.Structure):  # ebpf_scatter_desc
+    _fields_ = [("index", ctypes.c_void_p), ("count", ctypes.c_void_p), ("total", ctypes.c_void_p),
+                ("queue", ctypes.c_uint32), ("cap", ctypes.c_uint64),
+                ("src_frames", ctypes.c_void_p), ("src_bytes", ctypes.c_uint64),
+                ("src_offsets", ctypes.c_void_p), ("src_lens", ctypes.c_void_p),
+                ("src_verdict", ctypes.c_void_p), ("src_status", ctypes.c_void_p),
+                ("src_r0", ctypes.c_void_p),
+                ("frames", ctypes.c_void_p), ("offsets", ctypes.c_void_p),
+                ("lens", ctypes.c_void_p), ("stride", ctypes.c_uint64), ("n", ctypes.c_uint64),
+                ("verdict", ctypes.c_void_p), ("status", ctypes.c_void_p), ("r0", ctypes.c_void_p),
                 ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_uint64)]
 
 
@@ -154,6 +167,11 @@ def lib():
         L.ebpf_gather_workspace_bytes.argtypes = [u64]
         L.ebpf_gather_workspace_bytes.restype = u64
         L.ebpf_gather.argtypes = [ctypes.POINTER(GatherDesc), vp]
+    # (likewise a build from before the scatter)
+    if hasattr(L, "ebpf_scatter"):
+        L.ebpf_scatter_workspace_bytes.argtypes = [u64]
+        L.ebpf_scatter_workspace_bytes.restype = u64
+        L.ebpf_scatter.argtypes = [ctypes.POINTER(ScatterDesc), vp]
     L.ebpf_strerror.argtypes = [ctypes.c_int]
     L.ebpf_strerror.restype = ctypes.c_char_p
     L.ebpf_version.restype = ctypes.c_char_p

@@ -1,11 +1,13 @@
-"""Verdict queues and the packet gather (ebpf_verdict_queues / ebpf_gather, include/ebpf_emu.h).
+"""Verdict queues, the packet gather and the scatter back (ebpf_verdict_queues / ebpf_gather /
+ebpf_scatter, include/ebpf_emu.h).
 
 What a datapath does with a batch's verdicts: `verdict_queues` is the stable partition of the
 packet numbers by XDP action (xdp.rs:3-9 order, then other / fault), `gather` copies one queue's
-packets into a dense offsets + lens batch -- itself the input of a next `Program.run`. Both are
-launches of the gfx950 kernels in libebpfemu.so (csrc/queues.hip) on the caller's stream, with no
-host synchronisation: the queue's size is read on the device. Device memory and streams come from
-PyTorch (plumbing only).
+packets into a dense offsets + lens batch -- itself the input of a next `Program.run` -- and
+`scatter` puts that batch's packets and results back at the packets' own numbers; `two_stage` is
+the whole chain. All are launches of the gfx950 kernels in libebpfemu.so (csrc/queues.hip) on the
+caller's stream, with no host synchronisation: the queue's size is read on the device. Device
+memory and streams come from PyTorch (plumbing only).
 """
 from __future__ import annotations
 
@@ -19,6 +21,7 @@ from . import _lib
 # workgroup a whole number of GATHER_TILE queue positions
 QUEUES_RANGE, QUEUES_MAX_WGS = 4096, 1024
 GATHER_TILE, GATHER_MAX_WGS = 256, 1024
+SCATTER_TILE, SCATTER_MAX_WGS = GATHER_TILE, GATHER_MAX_WGS  # the scatter walks the same tiles
 MAX_OUT_BYTES = 1 << 32
 
 
@@ -121,3 +124,135 @@ def gather(frames, index, count, queue: int, *, stride: int = 0, offsets=None, l
     if rc:
         raise _lib.EbpfError(rc, "ebpf_gather")
     return res
+
+
+_RESULTS = (("verdict", "uint8"), ("status", "uint8"), ("r0", "int64"))
+
+
+def scatter(gathered, index, count, queue: int, *, frames=None, stride: int = 0, offsets=None,
+            lens=None, n: int | None = None, src=None, dst=None, cap: int | None = None,
+            stream=None) -> None:
+    """Put a gathered queue back (ebpf_scatter): queue position j of queue `queue` of (index,
+    count) is packet d = index[start + j] of the original batch.
+
+    gathered: the GatherResult the queue was gathered into (and a second Program.run perhaps
+    rewrote with writeback=True); its `total`, when set, bounds the positions scattered.
+    frames (+ stride / offsets / lens, n: the ORIGINAL batch as Program.run takes it): written --
+    bytes [0, min(gathered.lens[j], len(d))) of packet d become the dense packet's, and no other
+    byte changes. frames=None: results only.
+    src / dst: BatchResult-like objects (the second run's result, the merged result); for each of
+    verdict, status and r0 that BOTH hold, dst.x[d] = src.x[j]; every other entry of dst is
+    untouched. cap: entries present in the dense arrays (default: the shortest of them).
+    Asynchronous on `stream` (None = current), no host synchronisation: the queue's size is read
+    on the device. The d values are distinct for verdict_queues' index; the dense and the original
+    buffers must not overlap."""
+    import torch
+
+    if gathered is None:
+        raise ValueError("scatter: `gathered` is the GatherResult of the queue (gather's result)")
+    if not 0 <= queue < _lib.NQUEUES:
+        raise ValueError(f"scatter: queue must be in 0..{_lib.NQUEUES - 1}")
+    if index.dtype != torch.int32 or count.dtype != torch.int32 or count.numel() < _lib.NQUEUES:
+        raise ValueError("scatter: index / count are verdict_queues' torch.int32 tensors")
+    dev = index.device
+    s = _lib.ScatterDesc()
+    present = []  # the dense arrays: cap may not pass the shortest of them
+    if frames is not None:
+        if frames.dtype != torch.uint8 or not frames.is_contiguous() or frames.is_inference():
+            raise ValueError("scatter: frames must be a writable, contiguous torch.uint8 tensor")
+        if gathered.frames is None or gathered.offsets is None or gathered.lens is None:
+            raise ValueError("scatter: frames needs gathered.frames, .offsets and .lens")
+        if offsets is None and stride == 0:
+            raise ValueError("scatter: frames needs a packet layout (offsets or a stride)")
+        if gathered.offsets.dtype != torch.int32 or gathered.lens.dtype != torch.int16:
+            raise ValueError("scatter: gathered.offsets / .lens are torch.int32 / torch.int16")
+        s.frames = frames.data_ptr()
+        s.offsets = offsets.data_ptr() if offsets is not None else None
+        s.lens = lens.data_ptr() if lens is not None else None
+        s.stride = stride
+        # (an empty tensor has no storage; nothing of it is read)
+        s.src_frames = gathered.frames.data_ptr() or count.data_ptr()
+        s.src_bytes = gathered.frames.numel()
+        s.src_offsets = gathered.offsets.data_ptr() or count.data_ptr()
+        s.src_lens = gathered.lens.data_ptr() or count.data_ptr()
+        present += [gathered.offsets, gathered.lens]
+    pairs = []
+    for name, dt in _RESULTS:
+        a = getattr(src, name, None) if src is not None else None
+        b = getattr(dst, name, None) if dst is not None else None
+        if a is None or b is None:
+            continue
+        want = getattr(torch, dt)
+        if a.dtype != want or b.dtype != want or not a.is_contiguous() or not b.is_contiguous():
+            raise ValueError(f"scatter: src.{name} / dst.{name} must be contiguous torch.{dt}")
+        setattr(s, "src_" + name, a.data_ptr())
+        setattr(s, name, b.data_ptr())
+        present.append(a)
+        pairs.append(b)
+    if n is None:
+        n = (pairs[0].numel() if pairs else offsets.numel() if offsets is not None
+             else index.numel())
+    if n > index.numel() or any(b.numel() < n for b in pairs) or \
+            (frames is not None and offsets is not None and offsets.numel() < n) or \
+            (frames is not None and lens is not None and lens.numel() < n):
+        raise ValueError("scatter: n passes index, a dst array, offsets or lens")
+    room = min((t.numel() for t in present), default=0)
+    if cap is None:
+        cap = room
+    if not 0 <= cap <= room:
+        raise ValueError("scatter: cap passes the shortest dense array")
+    s.index = index.data_ptr() or count.data_ptr()  # (an empty tensor has no storage)
+    s.count = count.data_ptr()
+    s.total = gathered.total.data_ptr() if gathered.total is not None else None
+    s.queue = queue
+    s.cap = cap
+    s.n = n
+    with torch.cuda.device(dev):
+        rc = _lib.lib().ebpf_scatter(ctypes.byref(s), _stream_ptr(stream))
+    if rc:
+        raise _lib.EbpfError(rc, "ebpf_scatter")
+
+
+@dataclass
+class TwoStageResult:
+    merged: object = None    # BatchResult: verdict / status / r0 per ORIGINAL packet
+    first: object = None     # the first stage's BatchResult (queue_index / queue_count included)
+    second: object = None    # the second stage's BatchResult, numbered by queue position
+    gathered: object = None  # the GatherResult the second stage ran on
+    m: int = 0               # packets the second stage ran
+
+
+def two_stage(first, second, frames, *, n: int | None = None, stride: int = 0, offsets=None,
+              lens=None, queue: int = 2, writeback: bool = False, align: int = 16, stream=None,
+              **run_kw) -> TwoStageResult:
+    """Run `first` over the batch, `second` over the packets `first` put in `queue` (default
+    XDP_PASS), and merge: res.merged.verdict / .status / .r0 hold the second stage's result for
+    the packets of the queue and the first stage's for every other packet; with writeback=True the
+    second stage's rewrites (EBPF_BATCH_WRITEBACK) land in `frames`, in the packets' own places.
+
+    The steps, on one stream: first.run(queues=True) -> gather -> ONE HOST READ of total[0], the
+    size of the second batch -> second.run on the dense batch -> scatter into a clone of the first
+    run's verdict / status / r0 (and into `frames`). That read of total[0] (8 bytes, which waits
+    for the first run and the gather) is this chain's only synchronisation; nothing else here
+    waits for the device. run_kw (mem_size, max_steps, ...) goes to both runs."""
+    import torch
+
+    from .program import BatchResult
+
+    r1 = first.run(frames, n=n, stride=stride, offsets=offsets, lens=lens, verdict=True, r0=True,
+                   status=True, queues=True, stream=stream, **run_kw)
+    n = r1.verdict.numel()
+    g = gather(frames, r1.queue_index, r1.queue_count, queue, stride=stride, offsets=offsets,
+               lens=lens, align=align, stream=stream, n=n)
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        m = int(g.total[0]) & 0xFFFFFFFF  # the one host read
+        merged = BatchResult(verdict=r1.verdict.clone(), status=r1.status.clone(),
+                             r0=r1.r0.clone())
+    r2 = BatchResult()
+    if m:
+        r2 = second.run(g.frames, n=m, offsets=g.offsets, lens=g.lens, verdict=True, r0=True,
+                        status=True, writeback=writeback, stream=stream, **run_kw)
+        scatter(g, r1.queue_index, r1.queue_count, queue, frames=frames if writeback else None,
+                stride=stride, offsets=offsets, lens=lens, n=n, src=r2, dst=merged, cap=m,
+                stream=stream)
+    return TwoStageResult(merged=merged, first=r1, second=r2, gathered=g, m=m)

@@ -319,9 +319,11 @@ int ebpf_pcap_index(const uint8_t* buf, size_t nbytes, uint32_t* offsets, uint16
 
 /* ---- verdict queues and the packet gather: what a datapath does with a batch's verdicts ----
  * (new: no reference counterpart; the reference runs one packet and prints r0. The queues follow
- * the action enum, xdp.rs:3-9.) Both calls are asynchronous and ordered on `stream` as
- * ebpf_run_batch is, make no host synchronisation, and allocate nothing when a workspace is
- * passed: run -> queues -> gather -> run chains on one stream with no host round trip. */
+ * the action enum, xdp.rs:3-9.) The calls (ebpf_scatter below included) are asynchronous and
+ * ordered on `stream` as ebpf_run_batch is, make no host synchronisation, and allocate nothing
+ * when a workspace is passed: run -> queues -> gather chains on one stream and none of the three
+ * ever synchronises. The NEXT ebpf_run_batch takes its n from the host, though: running the
+ * gathered batch costs one 8-byte read of out_total, the chain's only host round trip. */
 
 /* Queue q holds the packets of verdict q for q = 0..4 (ABORTED, DROP, PASS, TX, REDIRECT);
  * queue 5 every other verdict byte but 0xFF (EBPF_VERDICT_OTHER; bytes 5..0xFD count here too);
@@ -384,6 +386,62 @@ uint64_t ebpf_gather_workspace_bytes(uint64_t n);
  * packet layout, queue >= EBPF_NQUEUES, align not a power of two in 1..256 or a workspace that is
  * too small; EBPF_ETOOBIG for out_bytes > 4 GiB or n > UINT32_MAX. */
 int ebpf_gather(const ebpf_gather_desc* g, ebpf_stream_t stream);
+
+/* The way back: a gathered queue's packets (as a second ebpf_run_batch left them, rewritten with
+ * EBPF_BATCH_WRITEBACK perhaps) and that run's per-packet results, put back at the packets' own
+ * numbers in the original batch. All pointers are DEVICE pointers; every src_ array and `frames`
+ * is optional. */
+typedef struct ebpf_scatter_desc {
+  const uint32_t* index;       /* ebpf_verdict_queues' index, u32[n] */
+  const uint32_t* count;       /* its count[EBPF_NQUEUES], READ ON THE DEVICE (no host sync) */
+  const uint32_t* total;       /* optional u32[2]: the gather's out_total (total[0] is read) */
+  uint32_t queue;              /* 0..EBPF_NQUEUES-1 */
+  uint64_t cap;                /* HOST value (<= UINT32_MAX): entries present in the src_ arrays, an
+                                  upper bound on the queue positions scattered; sizes the grid */
+  const uint8_t* src_frames;   /* the dense side: the gather's out_frames, u8[src_bytes], */
+  uint64_t src_bytes;          /*   <= 4 GiB, */
+  const uint32_t* src_offsets; /*   its out_offsets, u32[cap], */
+  const uint16_t* src_lens;    /*   its out_lens, u16[cap]; */
+  const uint8_t* src_verdict;  /*   the second run's outputs: u8[cap] (any alignment), */
+  const uint8_t* src_status;   /*   u8[cap] (any alignment), */
+  const uint64_t* src_r0;      /*   u64[cap] */
+  uint8_t* frames;             /* the destination batch, as in ebpf_batch and WRITTEN: packet i at */
+  const uint32_t* offsets;     /*   frames + offsets[i], or frames + i*stride when NULL; its length */
+  const uint16_t* lens;        /*   lens[i], or stride when NULL. frames == NULL: results only */
+  uint64_t stride;
+  uint64_t n;                  /* packets in the destination batch (<= UINT32_MAX) */
+  uint8_t* verdict;            /* u8[n] (any alignment), u8[n] (any alignment), u64[n]: each is */
+  uint8_t* status;             /*   written only when it and its src_ partner are both non-NULL */
+  uint64_t* r0;
+  void* workspace;             /* optional scratch of ebpf_scatter_workspace_bytes(cap) bytes */
+  uint64_t workspace_bytes;
+} ebpf_scatter_desc;
+
+/* 0 today: destinations and source offsets are both given, so the one kernel needs no scratch. */
+uint64_t ebpf_scatter_workspace_bytes(uint64_t cap);
+
+/* With start = count[0] + ... + count[queue-1] and m = min(count[queue], cap, total ? total[0] :
+ * UINT32_MAX) -- both clamped so that index is read inside index[0, n) only -- queue position
+ * j < m belongs to destination packet d = index[start + j]. An entry is VALID when d < n and, with
+ * `frames`, its source span lies inside the dense buffer: src_offsets[j] + src_lens[j] <=
+ * src_bytes. Once the call has completed on the stream, for every valid entry:
+ *   verdict[d] = src_verdict[j], status[d] = src_status[j], r0[d] = src_r0[j] (the pairs present);
+ *   with L = min(src_lens[j], len(d)), len(d) = lens[d] or stride: bytes [0, L) of packet d =
+ *   src_frames[src_offsets[j] .. + L). L == 0 writes no bytes; the results are still merged.
+ * Nothing else is written: not the entries of verdict / status / r0 that are no d, not one byte of
+ * `frames` outside those [0, L) -- the rest of a longer slot, the gap to the next packet, a
+ * neighbour that abuts at any alignment (a packet's partial first and last 16-byte pieces are
+ * stored with naturally aligned 1/2/4/8-byte stores, never by read-modify-write of a wider word)
+ * -- and nothing at all for an entry that is not valid: a wrong index never becomes a wild store.
+ * Reads of src_frames stay inside the aligned 16-byte blocks that hold a byte of the bytes copied.
+ * The d values must be distinct, destination packets must not overlap each other, and the dense
+ * and destination buffers must not overlap (none is checked; all hold for ebpf_verdict_queues'
+ * and ebpf_gather's outputs). cap == 0, an empty queue and nothing to write are valid.
+ * Returns, before any device call: EBPF_EINVAL for a NULL descriptor, index or count, queue >=
+ * EBPF_NQUEUES, frames without src_frames, src_offsets or src_lens, frames with neither offsets
+ * nor a non-zero stride, or a workspace that is too small; EBPF_ETOOBIG for n or cap > UINT32_MAX
+ * or src_bytes > 4 GiB. */
+int ebpf_scatter(const ebpf_scatter_desc* s, ebpf_stream_t stream);
 
 /* Human-readable message for an EBPF_E* code. */
 const char* ebpf_strerror(int err);
