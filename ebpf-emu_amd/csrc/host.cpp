@@ -2363,8 +2363,9 @@ int ebpf_pcap_index(const uint8_t* buf, size_t nbytes, uint32_t* offsets, uint16
 
 // ---- verdict queues and the gather (queues.hip) ----
 // Their library-owned scratch per (device, stream): a buffer of its own, [queues region][gather
-// region], so the batch workspace's zeroed counter shards are never touched. Both regions have a
-// fixed size (the grids are capped), so the buffer is allocated once and never grows.
+// region][pcap gather region], so the batch workspace's zeroed counter shards are never touched.
+// All regions have a fixed size (the grids are capped), so the buffer is allocated once and never
+// grows.
 static std::map<std::pair<int, void*>, void*> g_qws;
 
 static int queues_workspace(void* user, uint64_t user_bytes, uint64_t need, uint64_t lib_off,
@@ -2376,7 +2377,7 @@ static int queues_workspace(void* user, uint64_t user_bytes, uint64_t need, uint
   }
   std::lock_guard<std::mutex> lk(g_ws_mu);
   void*& p = g_qws[{device, (void*)s}];
-  if (!p && hipMalloc(&p, kQWsBytes + kGWsBytes) != hipSuccess) {
+  if (!p && hipMalloc(&p, kQWsBytes + kGWsBytes + kPWsBytes) != hipSuccess) {
     p = nullptr;
     return EBPF_ENOMEM;
   }
@@ -2499,6 +2500,59 @@ int ebpf_scatter(const ebpf_scatter_desc* d, ebpf_stream_t stream) {
   if (rc) return rc;
   DeviceScope on(device);
   return launch_scatter(a, s) == hipSuccess ? EBPF_OK : EBPF_EHIP;
+}
+
+uint64_t ebpf_pcap_gather_workspace_bytes(uint64_t n) {
+  (void)n;  // (the grid is capped: the per-workgroup sums have one size)
+  return kPWsBytes;
+}
+
+int ebpf_pcap_gather(const ebpf_pcap_gather_desc* p, ebpf_stream_t stream) {
+  static_assert(kPcapSrcRecords == EBPF_PCAP_SRC_RECORDS && kPcapSwapped == EBPF_PCAP_SWAPPED,
+                "include/ebpf_emu.h names the flags");
+  if (!p) return EBPF_EINVAL;
+  if (!p->index || !p->count || !p->out_total) return EBPF_EINVAL;
+  if ((p->n && !p->frames) || (p->out_bytes && !p->out)) return EBPF_EINVAL;
+  if (!p->offsets && p->stride == 0 && !p->lens) return EBPF_EINVAL;  // no packet layout
+  if (!p->lens && p->stride > 0xFFFF) return EBPF_EINVAL;             // (incl_len is a u16 here)
+  if (p->queue >= EBPF_NQUEUES) return EBPF_EINVAL;
+  if (p->flags & ~(EBPF_PCAP_SRC_RECORDS | EBPF_PCAP_SWAPPED)) return EBPF_EINVAL;
+  if (p->n > 0xFFFFFFFFull || p->out_bytes > (1ull << 32)) return EBPF_ETOOBIG;
+  if (p->workspace && (p->workspace_bytes < kPWsBytes || ((uintptr_t)p->workspace & 7)))
+    return EBPF_EINVAL;
+  if (p->n == 0) return EBPF_OK;  // no batch: nothing is launched, nothing is written
+  hipStream_t s = (hipStream_t)stream;
+  int device = 0;
+  int rc = stream_device(s, &device);
+  if (rc) return rc;
+  DeviceScope on(device);
+  uint8_t* ws = nullptr;
+  rc = queues_workspace(p->workspace, p->workspace_bytes, kPWsBytes, kQWsBytes + kGWsBytes, device,
+                        s, &ws);
+  if (rc) return rc;
+  PcapArgs a{};
+  a.frames = p->frames;
+  a.offsets = p->offsets;
+  a.lens = p->lens;
+  a.stride = p->stride;
+  a.n = p->n;
+  a.index = p->index;
+  a.count = p->count;
+  a.queue = p->queue;
+  a.flags = p->flags;
+  a.snaplen = p->snaplen;
+  memcpy(a.hdr, p->file_header, sizeof a.hdr);
+  a.ts = p->ts;
+  a.out = p->out;
+  // (offsets and the end byte are u32: a record is written only if it ends at or below 2^32 - 1)
+  a.cap = std::min<uint64_t>(p->out_bytes, 0xFFFFFFFFull);
+  a.out_offsets = p->out_offsets;
+  a.out_lens = p->out_lens;
+  a.out_total = p->out_total;
+  a.wsum = (unsigned long long*)ws;
+  a.wcnt = (uint32_t*)(ws + kPWsCntOff);
+  a.wfirst = (uint32_t*)(ws + kPWsFirstOff);
+  return launch_pcap_gather(a, s) == hipSuccess ? EBPF_OK : EBPF_EHIP;
 }
 
 const char* ebpf_strerror(int err) {

@@ -260,4 +260,38 @@ struct ScatterArgs {  // ebpf_scatter_desc, checked: a result pair is both set o
 // One kernel on `stream`, its grid sized from cap as the gather's is from n (kGTile, kGMaxWgs).
 hipError_t launch_scatter(const ScatterArgs& s, hipStream_t stream);
 
+// ---- the pcap gather: a queue written out as a classic libpcap stream (queues.hip, DESIGN.md
+// §3.40). Its workspace, per workgroup of the capped grid: [record bytes u64][records u32][bytes of
+// the first record u32]; no zeroing, every word read was written first.
+constexpr uint64_t kPWsCntOff = (uint64_t)kGMaxWgs * 8;
+constexpr uint64_t kPWsFirstOff = kPWsCntOff + (uint64_t)kGMaxWgs * 4;
+constexpr uint64_t kPWsBytes = kPWsFirstOff + (uint64_t)kGMaxWgs * 4;
+constexpr uint32_t kPcapSrcRecords = 1, kPcapSwapped = 2;  // EBPF_PCAP_SRC_RECORDS / _SWAPPED
+
+struct PcapArgs {  // ebpf_pcap_gather_desc, checked (cap = min(out_bytes, 2^32 - 1)); the source
+                   // batch and the queue under GatherArgs' names (g_queue / g_packet read both)
+  const uint8_t* frames;
+  const uint32_t* offsets;
+  const uint16_t* lens;
+  uint64_t stride;
+  uint64_t n;
+  const uint32_t* index;
+  const uint32_t* count;
+  uint32_t queue;
+  uint32_t flags;
+  uint32_t snaplen;
+  uint32_t hdr[6];      // the global header's 24 bytes
+  const uint32_t* ts;   // optional u32[n][2]
+  uint8_t* out;
+  uint64_t cap;
+  uint32_t* out_offsets;  // optional
+  uint16_t* out_lens;     // optional
+  uint32_t* out_total;
+  unsigned long long* wsum;  // workspace: u64[grid], u32[grid], u32[grid]
+  uint32_t* wcnt;
+  uint32_t* wfirst;
+};
+// Two kernels on `stream` (include/ebpf_emu.h ebpf_pcap_gather); n >= 1.
+hipError_t launch_pcap_gather(const PcapArgs& p, hipStream_t stream);
+
 }  // namespace ebpfemu

@@ -1,15 +1,16 @@
 // queues.hip — what a datapath does with a batch's verdicts: the stable
 // partition of the packet numbers by XDP action (ebpf_verdict_queues) and the copy of one queue's
 // packets into a dense offsets + lens batch (ebpf_gather), and the way back (§3.39): that dense
-// batch's packets and results put back at the packets' own numbers (ebpf_scatter, one launch).
+// batch's packets and results put back at the packets' own numbers (ebpf_scatter, one launch);
+// and the way out (§3.40): one queue written as a classic libpcap byte stream (ebpf_pcap_gather).
 // New: no reference counterpart (the reference runs one packet and prints r0); xdp.rs:3-9 is the
 // action enum the queues follow.
 //
-// The first two are count -> bases -> write over contiguous per-workgroup ranges, in separate launches:
-// the launch boundary is the only ordering between workgroups. No workgroup ever waits on
-// another one's progress (no look-back, no flag, no grid barrier, no cooperative launch), so a
-// grid larger than the resident set cannot hang. No device atomics; the only LDS atomics add up
-// sums whose order does not matter.
+// The queues and the two gathers are count -> bases -> write over contiguous per-workgroup ranges,
+// in separate launches: the launch boundary is the only ordering between workgroups. No workgroup
+// ever waits on another one's progress (no look-back, no flag, no grid barrier, no cooperative
+// launch), so a grid larger than the resident set cannot hang. No device atomics; the only LDS
+// atomics add up sums whose order does not matter.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -240,7 +241,8 @@ struct GQueue {
   uint32_t start, m;  // the queue is index[start .. start + m)
   uint64_t span;      // queue positions per workgroup
 };
-__device__ __forceinline__ GQueue g_queue(const GatherArgs& a, uint32_t grid) {
+template <class Args>  // GatherArgs, PcapArgs: the queue under the same names
+__device__ __forceinline__ GQueue g_queue(const Args& a, uint32_t grid) {
   uint64_t start = 0;
   for (uint32_t c = 0; c < a.queue; c++) start += a.count[c];
   uint64_t m = a.count[a.queue];
@@ -408,6 +410,231 @@ __global__ __launch_bounds__(kGTile) void gather_copy(GatherArgs a) {
     }
     B += pre[kGTile - 1];
     __syncthreads();  // (the next tile rewrites the LDS arrays)
+  }
+}
+
+// ============================================================================================
+// Pcap gather: the gather with a 16-byte record header in front of every packet
+// and the 24-byte global header in front of all. The layout is the gather's at align 1 with
+// 16 + incl in place of the length and a base of 24; a record is 1 + ceil(incl / 16) chunks at
+// record offset 16 c -- chunk 0 the header (built in registers, or loaded from the 16 bytes before
+// the packet), chunk c >= 1 the packet's bytes [16 (c - 1), ...), the last one stored byte-exact
+// -- dealt to the lanes as gather_copy deals its. A packet number outside the batch is no record
+// at all, so a record's number is not its queue position: pcap_sums also counts each range's
+// records and notes the size of its first one, and the totals are reported by the one workgroup
+// that can tell from those that its last written record is the last one (no atomics, no flags).
+// ============================================================================================
+struct PRec {
+  uint32_t i;          // the source packet number (>= n: no record)
+  uint32_t len, incl;  // its length, and the bytes of it the record holds
+  const uint8_t* src;
+};
+__device__ __forceinline__ PRec p_record(const PcapArgs& a, const GQueue& q, uint64_t j) {
+  PRec r;
+  r.i = a.index[q.start + j];
+  r.len = r.incl = 0;
+  r.src = a.frames;
+  if (r.i >= a.n) return r;  // (no address is formed from it)
+  r.src = a.frames + (a.offsets ? (uint64_t)a.offsets[r.i] : r.i * a.stride);
+  r.len = a.lens ? (uint32_t)a.lens[r.i] : (uint32_t)a.stride;
+  r.incl = (a.snaplen && a.snaplen < r.len) ? a.snaplen : r.len;
+  return r;
+}
+
+// Minimum over the workgroup (every thread gets it); red: u64[kGTile] in LDS.
+__device__ __forceinline__ uint64_t block_min(uint64_t v, unsigned long long* red, uint32_t t) {
+  __syncthreads();
+  red[t] = v;
+  __syncthreads();
+  for (uint32_t d = kGTile / 2; d > 0; d >>= 1) {
+    if (t < d && red[t + d] < red[t]) red[t] = red[t + d];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// Inclusive scan of v[kGTile] (LDS) in place, v[t] written by thread t just before the call
+// (gather_copy's scan steps).
+__device__ __forceinline__ void tile_scan(uint32_t* v, uint32_t t) {
+  __syncthreads();
+  for (uint32_t d = 1; d < kGTile; d <<= 1) {
+    const uint32_t x = t >= d ? v[t - d] : 0u;
+    __syncthreads();
+    v[t] += x;
+    __syncthreads();
+  }
+}
+
+// Per range: the bytes of its records, their number, and the bytes of the first one (0: none).
+__global__ __launch_bounds__(kGTile) void pcap_sums(PcapArgs a) {
+  __shared__ unsigned long long red[kGTile];
+  const uint32_t t = threadIdx.x, g = blockIdx.x;
+  const GQueue q = g_queue(a, gridDim.x);
+  const uint64_t beg = (uint64_t)g * q.span;
+  const uint64_t end = beg + q.span < q.m ? beg + q.span : q.m;
+  uint64_t sum = 0, cnt = 0;
+  uint64_t first = ~0ull;  // (position << 17 | record bytes) of the thread's first record
+  for (uint64_t j = beg + t; j < end; j += kGTile) {
+    const PRec r = p_record(a, q, j);
+    if (r.i >= a.n) continue;
+    sum += 16 + r.incl;
+    cnt++;
+    if (first == ~0ull) first = (j << 17) | (16 + r.incl);  // (j < 2^32, 16 + incl < 2^17)
+  }
+  sum = block_sum(sum, red, t);
+  cnt = block_sum(cnt, red, t);
+  first = block_min(first, red, t);
+  if (t == 0) {
+    a.wsum[g] = sum;
+    a.wcnt[g] = (uint32_t)cnt;
+    a.wfirst[g] = cnt ? (uint32_t)(first & 0x1FFFFu) : 0u;
+  }
+}
+
+__global__ __launch_bounds__(kGTile) void pcap_copy(PcapArgs a) {
+  // sc: (records written << kPShift | their chunks), scanned together: a tile has at most
+  // 256 * (1 + 4096) chunks
+  constexpr uint32_t kPShift = 22, kPMask = (1u << kPShift) - 1;
+  static_assert(kGTile * (1u + 65536u / 16u) <= kPMask && kGTile < (1u << (32 - kPShift)), "sc");
+  __shared__ uint32_t pre[kGTile], sc[kGTile], cpre[kGTile], len_s[kGTile], incl_s[kGTile], idx_s[kGTile];
+  __shared__ const uint8_t* src_s[kGTile];
+  __shared__ unsigned long long red[kGTile];
+  __shared__ uint32_t last_end;  // the end byte of the range's last written record
+  const uint32_t t = threadIdx.x, g = blockIdx.x, grid = gridDim.x;
+  const bool swap = (a.flags & kPcapSwapped) != 0;
+  if (g == 0 && t == 0) {  // the global header, and the totals when no record at all is written
+    if (a.cap < 24) {
+      a.out_total[0] = a.out_total[1] = 0;
+    } else {
+      *(u32x4_any*)a.out = u32x4{a.hdr[0], a.hdr[1], a.hdr[2], a.hdr[3]};
+      *(u64_any*)(a.out + 16) = (uint64_t)a.hdr[4] | ((uint64_t)a.hdr[5] << 32);
+      uint32_t k = 0;
+      while (k < grid && a.wcnt[k] == 0) k++;
+      if (k == grid || 24ull + a.wfirst[k] > a.cap) {
+        a.out_total[0] = 0;
+        a.out_total[1] = 24;
+      }
+    }
+  }
+  if (a.cap < 24) return;  // (uniform) no record fits
+  const GQueue q = g_queue(a, grid);
+  const uint64_t beg = (uint64_t)g * q.span;
+  const uint64_t end = beg + q.span < q.m ? beg + q.span : q.m;
+  if (beg >= end) return;  // (uniform)
+  uint64_t B = 0, R = 0;   // the output offset and the number of the range's first record
+  for (uint32_t k = t; k < g; k += kGTile) {
+    B += a.wsum[k];
+    R += a.wcnt[k];
+  }
+  B = 24 + block_sum(B, red, t);
+  R = block_sum(R, red, t);
+  uint32_t nwr = 0;      // records of this range written so far
+  bool stopped = false;  // a record of this range did not fit: no later one does (the ends ascend)
+  for (uint64_t tb = beg; tb < end && !stopped; tb += kGTile) {
+    const uint64_t j = tb + t;
+    PRec r;
+    r.i = 0xFFFFFFFFu, r.len = r.incl = 0, r.src = a.frames;
+    if (j < end) r = p_record(a, q, j);
+    const bool valid = j < end && r.i < a.n;
+    const uint32_t adv = valid ? 16 + r.incl : 0u;
+    pre[t] = adv;
+    tile_scan(pre, t);  // of the record sizes
+    const uint64_t off = B + pre[t] - adv;  // the record's first byte
+    const bool wr = valid && off + adv <= a.cap;
+    len_s[t] = r.len;
+    incl_s[t] = r.incl;
+    idx_s[t] = r.i;
+    src_s[t] = r.src;
+    sc[t] = wr ? (1u << kPShift) | (1 + (r.incl + 15) / 16) : 0u;
+    tile_scan(sc, t);  // of records written | chunks
+    const uint32_t rank = sc[t] >> kPShift, wc = sc[kGTile - 1] >> kPShift;
+    cpre[t] = sc[t] & kPMask;
+    if (wr) {  // the written records are a prefix of the records: the rank is the record number
+      const uint64_t rr = R + nwr + rank - 1;
+      if (a.out_offsets) a.out_offsets[rr] = (uint32_t)(off + 16);
+      if (a.out_lens) a.out_lens[rr] = (uint16_t)r.incl;
+      if (rank == wc) last_end = (uint32_t)(off + adv);
+    }
+    stopped = __syncthreads_or(valid && !wr) != 0;
+    // wave w copies the w-th quarter of the tile's chunks, lane l the chunks l, l + 64, ... of it,
+    // four in flight before any store (gather_copy's deal)
+    const uint32_t chunks = cpre[kGTile - 1];
+    const uint32_t wv = t >> 6, ln = t & 63, qc = (chunks + 3) / 4;
+    const uint32_t kb = min(wv * qc, chunks), ke = min(kb + qc, chunks);
+    uint32_t p = 0;
+    if (kb + ln < ke) {
+      uint32_t lo = 0, hi = kGTile - 1;  // (cpre[kGTile - 1] > k for every k < chunks)
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (cpre[mid] <= kb + ln) lo = mid + 1;
+        else hi = mid;
+      }
+      p = lo;
+    }
+    for (uint32_t k0 = kb + ln; k0 < ke; k0 += 4 * 64) {
+      u32x4 v[4];
+      uint8_t* dst[4];
+      uint32_t rem[4];  // 0: nothing, 16: the whole chunk, else that many bytes
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const uint32_t k = k0 + 64 * u;
+        rem[u] = 0;
+        dst[u] = a.out;
+        v[u] = u32x4{0u, 0u, 0u, 0u};
+        if (k >= ke) continue;
+        while (cpre[p] <= k) p++;
+        const uint32_t c = k - (p ? cpre[p - 1] : 0u);
+        const uint32_t lp = len_s[p], ip = incl_s[p];
+        const uint8_t* sp = src_s[p];
+        dst[u] = a.out + (B + pre[p] - (16 + ip) + 16ull * c);
+        if (c == 0) {  // the record header
+          rem[u] = 16;
+          if ((a.flags & kPcapSrcRecords) && (uintptr_t)sp - (uintptr_t)a.frames >= 16) {
+            const u32x4_any x = *(g_u4_any*)((uintptr_t)sp - 16);  // the source's own, as it lies
+            const uint32_t cut = swap ? __builtin_bswap32(ip) : ip;
+            v[u] = u32x4{x.x, x.y, ip < lp ? cut : x.z, x.w};
+          } else {
+            const uint32_t i = idx_s[p];
+            const uint32_t s0 = a.ts ? a.ts[2ull * i] : i, s1 = a.ts ? a.ts[2ull * i + 1] : 0u;
+            v[u] = swap ? u32x4{__builtin_bswap32(s0), __builtin_bswap32(s1),
+                                __builtin_bswap32(ip), __builtin_bswap32(lp)}
+                        : u32x4{s0, s1, ip, lp};
+          }
+          continue;
+        }
+        const uint32_t left = ip - 16 * (c - 1);
+        if (left >= 16) {  // inside the packet: one load, as it lies
+          const u32x4_any x = *(g_u4_any*)((uintptr_t)sp + 16ull * (c - 1));
+          v[u] = u32x4{x.x, x.y, x.z, x.w};
+          rem[u] = 16;
+        } else {  // the last, partial chunk: the next record's header starts right behind it
+          v[u] = tail_chunk(sp, ip, c - 1);
+          rem[u] = left;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        if (rem[u] == 16) *(u32x4_any*)dst[u] = v[u];
+        else if (rem[u]) store_bytes(dst[u], v[u], rem[u]);
+      }
+    }
+    nwr += wc;
+    B += pre[kGTile - 1];
+    __syncthreads();  // (the next tile rewrites the LDS arrays)
+  }
+  if (t == 0 && nwr) {
+    // this range's last written record is the last one of all iff the next record -- in this
+    // range, else the first one of the next range that has any -- does not fit or does not exist
+    bool last = stopped;
+    if (!last) {  // (every record of the range was written: B is where the next one starts)
+      uint32_t k = g + 1;
+      while (k < grid && a.wcnt[k] == 0) k++;
+      last = k == grid || B + a.wfirst[k] > a.cap;
+    }
+    if (last) {
+      a.out_total[0] = (uint32_t)(R + nwr);
+      a.out_total[1] = last_end;
+    }
   }
 }
 
@@ -619,6 +846,14 @@ hipError_t launch_gather(const GatherArgs& a, hipStream_t stream) {
   const int grid = (int)(g < 1 ? 1 : g > (uint64_t)kGMaxWgs ? (uint64_t)kGMaxWgs : g);
   hipLaunchKernelGGL(gather_sums, dim3(grid), dim3(kGTile), 0, stream, a);
   hipLaunchKernelGGL(gather_copy, dim3(grid), dim3(kGTile), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_pcap_gather(const PcapArgs& a, hipStream_t stream) {
+  const uint64_t g = (a.n + kGTile - 1) / kGTile;
+  const int grid = (int)(g < 1 ? 1 : g > (uint64_t)kGMaxWgs ? (uint64_t)kGMaxWgs : g);
+  hipLaunchKernelGGL(pcap_sums, dim3(grid), dim3(kGTile), 0, stream, a);
+  hipLaunchKernelGGL(pcap_copy, dim3(grid), dim3(kGTile), 0, stream, a);
   return hipGetLastError();
 }
 

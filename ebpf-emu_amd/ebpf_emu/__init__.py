@@ -17,7 +17,7 @@ def __getattr__(name):  # lazy: these import torch
 
         return getattr(program, name)
     if name in ("verdict_queues", "gather", "GatherResult", "scatter", "two_stage",
-                "TwoStageResult"):
+                "TwoStageResult", "pcap_gather"):
         from . import queues
 
         return getattr(queues, name)

@@ -54,6 +54,7 @@ EXPORTS = ["ebpf_batch_init", "ebpf_prog_load", "ebpf_prog_load_hex", "ebpf_prog
            "ebpf_pcap_index",
            "ebpf_queues_workspace_bytes", "ebpf_verdict_queues", "ebpf_gather_workspace_bytes",
            "ebpf_gather", "ebpf_scatter_workspace_bytes", "ebpf_scatter",
+           "ebpf_pcap_gather_workspace_bytes", "ebpf_pcap_gather",
            "ebpf_strerror", "ebpf_version"]
 
 
@@ -94,6 +95,23 @@ class ScatterDesc(ctypes.Structure):  # ebpf_scatter_desc
                 ("frames", ctypes.c_void_p), ("offsets", ctypes.c_void_p),
                 ("lens", ctypes.c_void_p), ("stride", ctypes.c_uint64), ("n", ctypes.c_uint64),
                 ("verdict", ctypes.c_void_p), ("status", ctypes.c_void_p), ("r0", ctypes.c_void_p),
+                ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_uint64)]
+
+
+PCAP_SRC_RECORDS = 1  # ebpf_pcap_gather_desc.flags: EBPF_PCAP_SRC_RECORDS (copy the source's record headers)
+PCAP_SWAPPED = 2      # EBPF_PCAP_SWAPPED (record header fields in the byte order opposite to the device's)
+
+
+class PcapGatherDesc(ctypes.Structure):  # ebpf_pcap_gather_desc
+    _fields_ = [("frames", ctypes.c_void_p), ("offsets", ctypes.c_void_p),
+                ("lens", ctypes.c_void_p), ("stride", ctypes.c_uint64), ("n", ctypes.c_uint64),
+                ("index", ctypes.c_void_p), ("count", ctypes.c_void_p),
+                ("queue", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("file_header", ctypes.c_uint8 * 24), ("snaplen", ctypes.c_uint32),
+                ("ts", ctypes.c_void_p),
+                ("out", ctypes.c_void_p), ("out_bytes", ctypes.c_uint64),
+                ("out_offsets", ctypes.c_void_p), ("out_lens", ctypes.c_void_p),
+                ("out_total", ctypes.c_void_p),
                 ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_uint64)]
 
 
@@ -172,6 +190,11 @@ def lib():
         L.ebpf_scatter_workspace_bytes.argtypes = [u64]
         L.ebpf_scatter_workspace_bytes.restype = u64
         L.ebpf_scatter.argtypes = [ctypes.POINTER(ScatterDesc), vp]
+    # (and one from before the pcap gather)
+    if hasattr(L, "ebpf_pcap_gather"):
+        L.ebpf_pcap_gather_workspace_bytes.argtypes = [u64]
+        L.ebpf_pcap_gather_workspace_bytes.restype = u64
+        L.ebpf_pcap_gather.argtypes = [ctypes.POINTER(PcapGatherDesc), vp]
     L.ebpf_strerror.argtypes = [ctypes.c_int]
     L.ebpf_strerror.restype = ctypes.c_char_p
     L.ebpf_version.restype = ctypes.c_char_p

@@ -10,6 +10,10 @@ chunk's bytes (offsets rebased to the chunk), H2D on one stream, the interpreter
 the verdict D2H on a third, with events so that chunk i+1's copy and chunk i-1's verdicts
 overlap chunk i's kernel. The reference reads one packet per process from argv (main.rs:14-22);
 this is its batched replacement for whole captures.
+
+`Capture.filter()` is the way back out: the records a program puts in one verdict queue, written
+on the device as a capture again (`queues.pcap_gather`, C ABI `ebpf_pcap_gather`) with their own
+record headers, one D2H copy per chunk.
 """
 from __future__ import annotations
 
@@ -33,6 +37,27 @@ def to_bytes(packets, linktype: int = LINKTYPE_ETHERNET, snaplen: int = 65535,
         out.append(struct.pack(e + "IIII", i, 0, len(p), len(p)))
         out.append(bytes(p))
     return b"".join(out)
+
+
+def header(linktype: int = LINKTYPE_ETHERNET, snaplen: int = 65535, nanos: bool = False,
+           big_endian: bool = False) -> tuple[bytes, int]:
+    """(the 24-byte global header, the matching queues.pcap_gather flag): to_bytes' header, and
+    _lib.PCAP_SWAPPED when its byte order is not the (little-endian) device's."""
+    e = ">" if big_endian else "<"
+    magic = 0xA1B23C4D if nanos else 0xA1B2C3D4
+    return (struct.pack(e + "IHHiIII", magic, 2, 4, 0, 0, snaplen, linktype),
+            _lib.PCAP_SWAPPED if big_endian else 0)
+
+
+def header_flag(file_header) -> int:
+    """The pcap_gather flag for a capture's own global header: PCAP_SWAPPED when its magic reads
+    as a1b2c3d4 / a1b23c4d big-endian."""
+    magic = bytes(file_header[:4])
+    if magic in (b"\xd4\xc3\xb2\xa1", b"\x4d\x3c\xb2\xa1"):
+        return 0
+    if magic in (b"\xa1\xb2\xc3\xd4", b"\xa1\xb2\x3c\x4d"):
+        return _lib.PCAP_SWAPPED
+    raise ValueError("not a classic pcap global header")
 
 
 def write(path: str, packets, **kw) -> None:
@@ -159,3 +184,53 @@ class Capture:
                 ev_out[k].record(s_out)
         torch.cuda.synchronize(dev)
         return verdict, counters
+
+    def filter(self, prog, queue: int = 2, writeback: bool = False, snaplen: int = 0,
+               packets_per_chunk: int = 1 << 20, mem_size: int = 1024, r10: int = 512,
+               second=None) -> bytes:
+        """The records `prog` puts in verdict queue `queue` (default XDP_PASS), as a new capture
+        in host bytes: the source's own global header, then each such record with its own header
+        (timestamps kept) in file order. writeback=True: the packets as `prog` rewrote them
+        (EBPF_BATCH_WRITEBACK on the device copy; the source capture is not changed). snaplen: cut
+        the records (0: no cut; orig_len is kept). second: a Program run over the queue's packets
+        before they are written out (queues.two_stage; with writeback=True its rewrites are what
+        the new capture holds, and `prog`'s own run does not write).
+
+        Chunked like run(): per chunk the bytes from its first record header on go to the device,
+        prog.run(queues=True) and ONE queues.pcap_gather with PCAP_SRC_RECORDS follow on the
+        current stream, and after one read of the chunk's out_total its records are appended; the
+        global header is kept from the first chunk only."""
+        import torch
+
+        from .queues import pcap_gather, pcap_out_bytes, two_stage
+
+        dev = self.device
+        file_header = bytes(self.host.numpy()[:24])
+        flags = _lib.PCAP_SRC_RECORDS | header_flag(file_header)
+        parts = [file_header]
+        chunks = self.chunks(packets_per_chunk)
+        if not chunks:
+            return file_header
+        max_bytes = max(e - b for _, _, b, e in chunks) + 16
+        max_pk = max(c for _, c, _, _ in chunks)
+        with torch.cuda.device(dev):
+            dframes = torch.empty(max_bytes, dtype=torch.uint8, device=dev)
+            out = torch.empty(pcap_out_bytes(max_bytes, max_pk, 0, True), dtype=torch.uint8, device=dev)
+            total = torch.empty(2, dtype=torch.int32, device=dev)
+            for i, c, b, e in chunks:
+                b -= 16  # the first record's header comes along: every packet offset is >= 16
+                dframes[:e - b].copy_(self.host[b:e], non_blocking=True)
+                offs = torch.from_numpy((self.offsets[i:i + c] - np.uint32(b)).view(np.int32)).to(dev)
+                lens = torch.from_numpy(self.lens[i:i + c].view(np.int16)).to(dev)
+                if second is not None:
+                    res = two_stage(prog, second, dframes, n=c, offsets=offs, lens=lens,
+                                    queue=queue, writeback=writeback, mem_size=mem_size, r10=r10).first
+                else:
+                    res = prog.run(dframes, n=c, offsets=offs, lens=lens, mem_size=mem_size,
+                                   r10=r10, queues=True, writeback=writeback)
+                pcap_gather(dframes, res.queue_index, res.queue_count, queue, file_header,
+                            flags=flags, snaplen=snaplen, offsets=offs, lens=lens, n=c, out=out,
+                            total=total)
+                end = int(total[1]) & 0xFFFFFFFF  # the one host read
+                parts.append(out[24:end].cpu().numpy().tobytes())
+        return b"".join(parts)

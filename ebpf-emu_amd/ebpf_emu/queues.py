@@ -1,13 +1,14 @@
-"""Verdict queues, the packet gather and the scatter back (ebpf_verdict_queues / ebpf_gather /
-ebpf_scatter, include/ebpf_emu.h).
+"""Verdict queues, the packet gather, the scatter back and the pcap gather (ebpf_verdict_queues /
+ebpf_gather / ebpf_scatter / ebpf_pcap_gather, include/ebpf_emu.h).
 
 What a datapath does with a batch's verdicts: `verdict_queues` is the stable partition of the
 packet numbers by XDP action (xdp.rs:3-9 order, then other / fault), `gather` copies one queue's
 packets into a dense offsets + lens batch -- itself the input of a next `Program.run` -- and
 `scatter` puts that batch's packets and results back at the packets' own numbers; `two_stage` is
-the whole chain. All are launches of the gfx950 kernels in libebpfemu.so (csrc/queues.hip) on the
-caller's stream, with no host synchronisation: the queue's size is read on the device. Device
-memory and streams come from PyTorch (plumbing only).
+the whole chain; `pcap_gather` writes one queue out as a classic pcap capture. All are launches of
+the gfx950 kernels in libebpfemu.so (csrc/queues.hip) on the caller's stream, with no host
+synchronisation: the queue's size is read on the device. Device memory and streams come from
+PyTorch (plumbing only).
 """
 from __future__ import annotations
 
@@ -256,3 +257,92 @@ def two_stage(first, second, frames, *, n: int | None = None, stride: int = 0, o
                 stride=stride, offsets=offsets, lens=lens, n=n, src=r2, dst=merged, cap=m,
                 stream=stream)
     return TwoStageResult(merged=merged, first=r1, second=r2, gathered=g, m=m)
+
+
+def pcap_out_bytes(frames_bytes: int, n: int, stride: int, has_lens: bool) -> int:
+    """Room for every packet of the batch as a record: the global header, n record headers and
+    the gather's bound on the packets' bytes at align 1, capped at 4 GiB."""
+    return min(24 + 16 * n + default_out_bytes(frames_bytes, n, stride, has_lens, 1), MAX_OUT_BYTES)
+
+
+def pcap_gather(frames, index, count, queue: int, file_header, *, flags: int = 0, snaplen: int = 0,
+                ts=None, stride: int = 0, offsets=None, lens=None, n: int | None = None,
+                out=None, total=None, out_offsets=None, out_lens=None, with_index: bool = False,
+                stream=None):
+    """Write queue `queue` of (index, count) out of the batch (frames, stride / offsets / lens: as
+    Program.run takes them) as a classic libpcap byte stream (ebpf_pcap_gather): file_header (24
+    bytes, pcap.header's or the source capture's own) at out[0:24], then one record per packet of
+    the queue. -> (out, total), total = [records written, end byte]: out[:total[1]] is the
+    capture. With with_index=True (or out_offsets / out_lens given) -> (out, total, out_offsets,
+    out_lens): each record's packet offset in `out` and its captured length, entries [0, total[0]).
+
+    flags: _lib.PCAP_SRC_RECORDS (the batch is a capture in place: copy its record headers),
+    _lib.PCAP_SWAPPED (a big-endian capture). snaplen: 0 = no cut. ts: optional torch.int32 [n, 2]
+    (u32 bits) seconds and fraction by source packet number; without it (and without SRC_RECORDS)
+    the timestamp is the source packet number. out / total / out_offsets / out_lens: optional
+    tensors to write into (sentinels, reuse); `out` defaults to room for the whole batch.
+    Asynchronous on `stream` (None = current), no host synchronisation."""
+    import torch
+
+    if not 0 <= queue < _lib.NQUEUES:
+        raise ValueError(f"pcap_gather: queue must be in 0..{_lib.NQUEUES - 1}")
+    if index.dtype != torch.int32 or count.dtype != torch.int32 or count.numel() < _lib.NQUEUES:
+        raise ValueError("pcap_gather: index / count are verdict_queues' torch.int32 tensors")
+    if frames.dtype != torch.uint8 or not frames.is_contiguous():
+        raise ValueError("pcap_gather: frames must be a contiguous torch.uint8 tensor")
+    hdr = bytes(file_header)
+    if len(hdr) != 24:
+        raise ValueError("pcap_gather: file_header is the 24-byte global header")
+    if flags & ~(_lib.PCAP_SRC_RECORDS | _lib.PCAP_SWAPPED):
+        raise ValueError("pcap_gather: flags are PCAP_SRC_RECORDS | PCAP_SWAPPED")
+    if not 0 <= snaplen <= 0xFFFFFFFF:
+        raise ValueError("pcap_gather: snaplen is a u32 (0: no cut)")
+    if offsets is None and lens is None and stride == 0:
+        raise ValueError("pcap_gather: needs a packet layout (offsets, lens or a stride)")
+    if n is None:
+        n = index.numel()
+    if n > index.numel() or (offsets is not None and offsets.numel() < n) or \
+            (lens is not None and lens.numel() < n):
+        raise ValueError("pcap_gather: n passes index, offsets or lens")
+    if ts is not None and (ts.dtype != torch.int32 or not ts.is_contiguous() or ts.numel() < 2 * n):
+        raise ValueError("pcap_gather: ts must be a contiguous torch.int32 [n, 2] tensor")
+    dev = frames.device
+    if out is None:
+        out = torch.empty(pcap_out_bytes(frames.numel(), n, stride, lens is not None),
+                          dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() > MAX_OUT_BYTES:
+        raise ValueError("pcap_gather: out must be a contiguous torch.uint8 tensor of at most 4 GiB")
+    if total is None:
+        total = torch.empty(2, dtype=torch.int32, device=dev)
+    if with_index or out_offsets is not None or out_lens is not None:
+        if out_offsets is None:
+            out_offsets = torch.empty(n, dtype=torch.int32, device=dev)
+        if out_lens is None:
+            out_lens = torch.empty(n, dtype=torch.int16, device=dev)
+        if out_offsets.dtype != torch.int32 or out_lens.dtype != torch.int16 or \
+                out_offsets.numel() < n or out_lens.numel() < n:
+            raise ValueError("pcap_gather: out_offsets / out_lens are torch.int32 / torch.int16 [n]")
+        with_index = True
+    p = _lib.PcapGatherDesc()
+    p.frames = frames.data_ptr() or total.data_ptr()  # (an empty tensor has no storage)
+    p.offsets = offsets.data_ptr() if offsets is not None else None
+    p.lens = lens.data_ptr() if lens is not None else None
+    p.stride = stride
+    p.n = n
+    p.index = index.data_ptr() or total.data_ptr()
+    p.count = count.data_ptr()
+    p.queue = queue
+    p.flags = flags
+    p.file_header[:] = hdr
+    p.snaplen = snaplen
+    p.ts = ts.data_ptr() if ts is not None else None
+    p.out = out.data_ptr() if out.numel() else None
+    p.out_bytes = out.numel()
+    p.out_offsets = (out_offsets.data_ptr() or None) if with_index else None
+    p.out_lens = (out_lens.data_ptr() or None) if with_index else None
+    p.out_total = total.data_ptr()
+    with torch.cuda.device(dev):
+        rc = _lib.lib().ebpf_pcap_gather(ctypes.byref(p), _stream_ptr(stream))
+    if rc:
+        raise _lib.EbpfError(rc, "ebpf_pcap_gather")
+    return (out, total, out_offsets, out_lens) if with_index else (out, total)

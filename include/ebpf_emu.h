@@ -443,6 +443,75 @@ uint64_t ebpf_scatter_workspace_bytes(uint64_t cap);
  * or src_bytes > 4 GiB. */
 int ebpf_scatter(const ebpf_scatter_desc* s, ebpf_stream_t stream);
 
+/* The way out: one queue written as a classic libpcap byte stream -- the 24-byte global header,
+ * then one record (16-byte record header + packet bytes) per packet of the queue, abutting. One
+ * D2H copy of out[0, out_total[1]) is a capture file; out / out_offsets / out_lens with n =
+ * out_total[0] is also an offsets + lens batch again (a capture in place, as ebpf_pcap_index
+ * gives). All pointers are DEVICE pointers but file_header. */
+#define EBPF_PCAP_SRC_RECORDS 1u /* the source batch is a capture in place: the 16 bytes before a
+                                    packet are its record header, copied instead of synthesised */
+#define EBPF_PCAP_SWAPPED     2u /* the record headers' fields are in the byte order opposite to
+                                    the device's (a big-endian capture on this little-endian GPU) */
+typedef struct ebpf_pcap_gather_desc {
+  const uint8_t* frames;    /* the source batch, index, count and queue: exactly as in */
+  const uint32_t* offsets;  /*   ebpf_gather_desc (packet i at frames + offsets[i], or frames + */
+  const uint16_t* lens;     /*   i*stride when NULL; its length lens[i], or stride when NULL, then */
+  uint64_t stride;          /*   stride <= 65535) */
+  uint64_t n;               /* packets in the source batch (<= UINT32_MAX) */
+  const uint32_t* index;    /* ebpf_verdict_queues' index, u32[n] */
+  const uint32_t* count;    /* its count[EBPF_NQUEUES], READ ON THE DEVICE (no host sync) */
+  uint32_t queue;           /* 0..EBPF_NQUEUES-1 */
+  uint32_t flags;           /* EBPF_PCAP_* */
+  uint8_t file_header[24];  /* HOST bytes, by value: the global header, written verbatim at output
+                               byte 0 (the caller builds it, or copies the source capture's own) */
+  uint32_t snaplen;         /* 0: no cut; else incl = min(len, snaplen) */
+  const uint32_t* ts;       /* optional u32[n][2] (4-byte aligned), by SOURCE packet number: the
+                               record's seconds and fraction (micro- or nanoseconds) */
+  uint8_t* out;             /* u8[out_bytes] */
+  uint64_t out_bytes;       /* <= 4 GiB (u32 offsets) */
+  uint32_t* out_offsets;    /* optional u32[n]: record r's packet offset inside out */
+  uint16_t* out_lens;       /* optional u16[n]: record r's incl */
+  uint32_t* out_total;      /* u32[2], OVERWRITTEN: records written, the end byte */
+  void* workspace;          /* optional scratch of ebpf_pcap_gather_workspace_bytes(n) bytes (8-byte
+                               aligned, no zeroing); NULL => library-owned per (device, stream) */
+  uint64_t workspace_bytes;
+} ebpf_pcap_gather_desc;
+
+uint64_t ebpf_pcap_gather_workspace_bytes(uint64_t n);
+
+/* With m = count[queue] and s_j = index[start + j] the j-th packet number of that queue (start,
+ * m clamped into index[0, n) as ebpf_scatter's): an entry with s_j >= n (none comes from
+ * ebpf_verdict_queues) is NO RECORD -- nothing is written for it and no address is formed from it.
+ * The others, in queue order, are the records r = 0, 1, ...; for record r of packet s:
+ *   len = lens[s] or stride; incl = snaplen && snaplen < len ? snaplen : len;
+ *   the record starts at byte 24 + the sum over earlier records of (16 + incl), its packet bytes
+ *   16 bytes later (out_offsets[r]; out_lens[r] = incl); records abut, no padding anywhere;
+ *   the packet bytes are the packet's first incl bytes as they are in `frames` when the call runs
+ *   on the stream (after an EBPF_BATCH_WRITEBACK batch: the rewritten bytes);
+ *   the 16 header bytes are four u32 {ts[s][0], ts[s][1], incl, len} -- {s, 0, incl, len} with ts
+ *   == NULL: the source packet number as the timestamp -- each byte-swapped under
+ *   EBPF_PCAP_SWAPPED. Under EBPF_PCAP_SRC_RECORDS a packet whose offset in frames (offsets[s] or
+ *   s*stride) is >= 16 gets the 16 bytes before it instead, verbatim, but for the third field,
+ *   which becomes incl (swapped under EBPF_PCAP_SWAPPED) when incl < len; the fourth (orig_len)
+ *   is kept. A packet at an offset < 16 gets the synthesised header: nothing before `frames` is
+ *   ever read.
+ * Record r is written iff it ends at or below out_bytes (and 2^32 - 1); the ends ascend, so the
+ * written records are a prefix, and out_total = {records written, end byte of the last one}, {0,
+ * 24} with none. The global header is written iff out_bytes >= 24; otherwise out_total = {0, 0}.
+ * Every byte of out at or past out_total[1] and every entry of out_offsets / out_lens at or past
+ * out_total[0] is untouched (a record's last bytes are stored byte-exact: a neighbouring record is
+ * never written twice and no wider word is read-modify-written). Source and output must not
+ * overlap (not checked). Reads of frames stay inside the aligned 16-byte blocks that hold a byte
+ * of a packet's first incl bytes, plus the 16 header bytes under EBPF_PCAP_SRC_RECORDS.
+ * Asynchronous on `stream`, no host synchronisation (m is read on the device, the grid is sized
+ * from n), two launches, no allocation when a workspace is passed. n == 0 is valid, launches
+ * nothing and writes NOTHING (out_total included): there is no batch. Returns, before any device
+ * call: EBPF_EINVAL for a NULL descriptor, index, count or out_total, a NULL frames with n > 0, a
+ * NULL out with out_bytes > 0, no packet layout, stride > 65535 without lens, queue >=
+ * EBPF_NQUEUES, a flag bit other than EBPF_PCAP_*, or a workspace that is too small or not 8-byte
+ * aligned; EBPF_ETOOBIG for out_bytes > 4 GiB or n > UINT32_MAX. */
+int ebpf_pcap_gather(const ebpf_pcap_gather_desc* p, ebpf_stream_t stream);
+
 /* Human-readable message for an EBPF_E* code. */
 const char* ebpf_strerror(int err);
 
