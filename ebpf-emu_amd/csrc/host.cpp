@@ -2363,7 +2363,8 @@ int ebpf_pcap_index(const uint8_t* buf, size_t nbytes, uint32_t* offsets, uint16
 
 // ---- verdict queues and the gather (queues.hip) ----
 // Their library-owned scratch per (device, stream): a buffer of its own, [queues region][gather
-// region][pcap gather region], so the batch workspace's zeroed counter shards are never touched.
+// region][pcap gather region][steer region], so the batch workspace's zeroed counter shards are
+// never touched.
 // All regions have a fixed size (the grids are capped), so the buffer is allocated once and never
 // grows.
 static std::map<std::pair<int, void*>, void*> g_qws;
@@ -2377,7 +2378,7 @@ static int queues_workspace(void* user, uint64_t user_bytes, uint64_t need, uint
   }
   std::lock_guard<std::mutex> lk(g_ws_mu);
   void*& p = g_qws[{device, (void*)s}];
-  if (!p && hipMalloc(&p, kQWsBytes + kGWsBytes + kPWsBytes) != hipSuccess) {
+  if (!p && hipMalloc(&p, kQWsBytes + kGWsBytes + kPWsBytes + kSWsBytes) != hipSuccess) {
     p = nullptr;
     return EBPF_ENOMEM;
   }
@@ -2553,6 +2554,93 @@ int ebpf_pcap_gather(const ebpf_pcap_gather_desc* p, ebpf_stream_t stream) {
   a.wcnt = (uint32_t*)(ws + kPWsCntOff);
   a.wfirst = (uint32_t*)(ws + kPWsFirstOff);
   return launch_pcap_gather(a, s) == hipSuccess ? EBPF_OK : EBPF_EHIP;
+}
+
+// ---- RSS flow steering (steer.hip) ----
+int ebpf_rss_hash(const ebpf_rss_desc* r, ebpf_stream_t stream) {
+  static_assert(kRssTypes == (EBPF_RSS_IPV4 | EBPF_RSS_IPV4_TCP | EBPF_RSS_IPV4_UDP | EBPF_RSS_IPV6 |
+                              EBPF_RSS_IPV6_TCP | EBPF_RSS_IPV6_UDP) &&
+                    sizeof r->key == kRssKeyBytes,
+                "include/ebpf_emu.h names the types and the key");
+  if (!r || !r->hash) return EBPF_EINVAL;
+  if (r->n && !r->frames) return EBPF_EINVAL;
+  if (!r->offsets && r->stride == 0 && !r->lens) return EBPF_EINVAL;  // no packet layout
+  if (!r->lens && r->stride > 0xFFFF) return EBPF_EINVAL;
+  if (r->types == 0 || (r->types & ~kRssTypes)) return EBPF_EINVAL;
+  if (r->n > 0xFFFFFFFFull) return EBPF_ETOOBIG;
+  if (r->n == 0) return EBPF_OK;  // nothing is launched
+  RssArgs a{};
+  a.frames = r->frames;
+  a.offsets = r->offsets;
+  a.lens = r->lens;
+  a.stride = r->stride;
+  a.n = r->n;
+  a.types = r->types;
+  a.hash = r->hash;
+  a.type = r->type;
+  // the window at input bit i: key bits [i, i + 32), out of the 5 key bytes that hold them (the
+  // last window ends at key bit 319)
+  for (int i = 0; i < kRssWindows; i++) {
+    uint64_t acc = 0;
+    for (int k = 0; k < 5; k++) acc = (acc << 8) | r->key[i / 8 + k];
+    a.win[i] = (uint32_t)(acc >> (8 - i % 8));
+  }
+  hipStream_t s = (hipStream_t)stream;
+  int device = 0;
+  int rc = stream_device(s, &device);
+  if (rc) return rc;
+  DeviceScope on(device);
+  return launch_rss_hash(a, s) == hipSuccess ? EBPF_OK : EBPF_EHIP;
+}
+
+uint64_t ebpf_steer_workspace_bytes(uint64_t n, uint32_t nq) {
+  (void)n, (void)nq;  // (the grid is capped and the counts are kept 64 to a row: one size)
+  return kSWsBytes;
+}
+
+int ebpf_steer(const uint32_t* key, uint64_t n, uint32_t nq, const uint16_t* reta,
+               uint32_t reta_len, uint32_t* index, uint32_t* bounds, void* workspace,
+               uint64_t workspace_bytes, ebpf_stream_t stream) {
+  static_assert(kSClasses == EBPF_STEER_MAX_QUEUES && kSReta == EBPF_STEER_MAX_RETA,
+                "include/ebpf_emu.h names the limits");
+  if (n > 0xFFFFFFFFull) return EBPF_ETOOBIG;
+  if (nq < 1 || nq > EBPF_STEER_MAX_QUEUES) return EBPF_EINVAL;
+  if (!bounds || (n && (!key || !index))) return EBPF_EINVAL;
+  if (workspace && (workspace_bytes < kSWsBytes || ((uintptr_t)workspace & 7))) return EBPF_EINVAL;
+  SteerArgs a{};
+  if (reta) {
+    if (reta_len < 1 || reta_len > EBPF_STEER_MAX_RETA || (reta_len & (reta_len - 1)))
+      return EBPF_EINVAL;
+    for (uint32_t j = 0; j < reta_len; j++) {
+      if (reta[j] >= nq) return EBPF_EINVAL;
+      a.reta[j] = (uint8_t)reta[j];
+    }
+  } else {  // Linux's default indirection table
+    reta_len = EBPF_STEER_MAX_RETA;
+    for (uint32_t j = 0; j < reta_len; j++) a.reta[j] = (uint8_t)(j % nq);
+  }
+  a.key = key;
+  a.n = n;
+  a.nq = nq;
+  a.mask = reta_len - 1;
+  while ((1u << a.bits) < nq) a.bits++;
+  a.index = index;
+  a.bounds = bounds;
+  hipStream_t s = (hipStream_t)stream;
+  int device = 0;
+  int rc = stream_device(s, &device);
+  if (rc) return rc;
+  DeviceScope on(device);
+  if (n == 0)
+    return hipMemsetAsync(bounds, 0, 2ull * nq * sizeof(uint32_t), s) == hipSuccess ? EBPF_OK
+                                                                                     : EBPF_EHIP;
+  uint8_t* ws = nullptr;
+  rc = queues_workspace(workspace, workspace_bytes, kSWsBytes, kQWsBytes + kGWsBytes + kPWsBytes,
+                        device, s, &ws);
+  if (rc) return rc;
+  a.wgc = (uint32_t*)ws;
+  a.wvc = (uint32_t*)(ws + kSWsWaveOff);
+  return launch_steer(a, s) == hipSuccess ? EBPF_OK : EBPF_EHIP;
 }
 
 const char* ebpf_strerror(int err) {

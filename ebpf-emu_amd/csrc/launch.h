@@ -294,4 +294,54 @@ struct PcapArgs {  // ebpf_pcap_gather_desc, checked (cap = min(out_bytes, 2^32 
 // Two kernels on `stream` (include/ebpf_emu.h ebpf_pcap_gather); n >= 1.
 hipError_t launch_pcap_gather(const PcapArgs& p, hipStream_t stream);
 
+// ---- RSS flow steering (steer.hip) ----
+constexpr int kRssBlock = 256;            // one lane per packet
+constexpr int kRssMaxWgs = 2048;          // hash grid cap (a larger batch: several passes)
+constexpr int kRssKeyBytes = 40;
+constexpr int kRssWindows = 288;          // input bits of the longest input (36 bytes)
+constexpr uint32_t kRssTypes = 63;        // every EBPF_RSS_* bit
+
+struct RssArgs {  // ebpf_rss_desc, checked
+  const uint8_t* frames;
+  const uint32_t* offsets;
+  const uint16_t* lens;
+  uint64_t stride;
+  uint64_t n;
+  uint32_t types;
+  uint32_t* hash;
+  uint8_t* type;  // optional
+  // win[i] = key bits [i, i + 32) as a number: what input bit i XORs into the hash. Uniform over
+  // the launch, read by constant index: the kernel holds them in scalar registers.
+  uint32_t win[kRssWindows];
+};
+// One kernel on `stream` (include/ebpf_emu.h ebpf_rss_hash); n >= 1.
+hipError_t launch_rss_hash(const RssArgs& r, hipStream_t stream);
+
+constexpr int kSBlock = 256;              // steer: 4 waves per workgroup
+constexpr int kSWaves = kSBlock / kWave;
+constexpr int kSClasses = 64;             // EBPF_STEER_MAX_QUEUES: counts are kept 64 to a row
+constexpr int kSReta = 128;               // EBPF_STEER_MAX_RETA
+constexpr uint32_t kSRange = 4096;        // a workgroup's keys: a whole number of these, one while
+                                          // the grid is not capped (each wave a quarter)
+constexpr int kSMaxWgs = 1024;            // steer grid cap (a larger batch: longer ranges)
+// workspace: [workgroup counts, then bases, u32[kSMaxWgs][64]][wave counts u32[kSMaxWgs][4][64]].
+// No zeroing: every word read was written first.
+constexpr uint64_t kSWsWaveOff = (uint64_t)kSMaxWgs * kSClasses * 4;
+constexpr uint64_t kSWsBytes = kSWsWaveOff + (uint64_t)kSMaxWgs * kSWaves * kSClasses * 4;
+
+struct SteerArgs {  // ebpf_steer's arguments, checked
+  const uint32_t* key;
+  uint64_t n;
+  uint32_t nq;
+  uint32_t mask;   // reta_len - 1
+  uint32_t bits;   // class bits that can be set: ceil(log2(nq))
+  uint32_t* index;
+  uint32_t* bounds;
+  uint32_t* wgc;   // workspace
+  uint32_t* wvc;
+  uint8_t reta[kSReta];  // entries < nq <= 64
+};
+// Three kernels on `stream` (include/ebpf_emu.h ebpf_steer); n >= 1.
+hipError_t launch_steer(const SteerArgs& s, hipStream_t stream);
+
 }  // namespace ebpfemu

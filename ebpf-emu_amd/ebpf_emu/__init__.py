@@ -21,6 +21,10 @@ def __getattr__(name):  # lazy: these import torch
         from . import queues
 
         return getattr(queues, name)
+    if name in ("rss_hash", "steer", "SteerResult", "MSFT_KEY", "SYMMETRIC_KEY"):
+        from . import rss
+
+        return getattr(rss, name)
     if name in ("Emu", "EmuPanic"):
         from . import emu
 

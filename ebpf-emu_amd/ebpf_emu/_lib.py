@@ -55,6 +55,7 @@ EXPORTS = ["ebpf_batch_init", "ebpf_prog_load", "ebpf_prog_load_hex", "ebpf_prog
            "ebpf_queues_workspace_bytes", "ebpf_verdict_queues", "ebpf_gather_workspace_bytes",
            "ebpf_gather", "ebpf_scatter_workspace_bytes", "ebpf_scatter",
            "ebpf_pcap_gather_workspace_bytes", "ebpf_pcap_gather",
+           "ebpf_rss_hash", "ebpf_steer_workspace_bytes", "ebpf_steer",
            "ebpf_strerror", "ebpf_version"]
 
 
@@ -113,6 +114,19 @@ class PcapGatherDesc(ctypes.Structure):  # ebpf_pcap_gather_desc
                 ("out_offsets", ctypes.c_void_p), ("out_lens", ctypes.c_void_p),
                 ("out_total", ctypes.c_void_p),
                 ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_uint64)]
+
+
+# ebpf_rss_desc.types: the EBPF_RSS_* input types
+RSS_IPV4, RSS_IPV4_TCP, RSS_IPV4_UDP, RSS_IPV6, RSS_IPV6_TCP, RSS_IPV6_UDP = 1, 2, 4, 8, 16, 32
+RSS_ALL = 63
+STEER_MAX_QUEUES, STEER_MAX_RETA = 64, 128  # EBPF_STEER_MAX_QUEUES / _RETA
+
+
+class RssDesc(ctypes.Structure):  # ebpf_rss_desc
+    _fields_ = [("frames", ctypes.c_void_p), ("offsets", ctypes.c_void_p),
+                ("lens", ctypes.c_void_p), ("stride", ctypes.c_uint64), ("n", ctypes.c_uint64),
+                ("key", ctypes.c_uint8 * 40), ("types", ctypes.c_uint32),
+                ("hash", ctypes.c_void_p), ("type", ctypes.c_void_p)]
 
 
 class EbpfError(RuntimeError):
@@ -195,6 +209,12 @@ def lib():
         L.ebpf_pcap_gather_workspace_bytes.argtypes = [u64]
         L.ebpf_pcap_gather_workspace_bytes.restype = u64
         L.ebpf_pcap_gather.argtypes = [ctypes.POINTER(PcapGatherDesc), vp]
+    # (and one from before the flow steering)
+    if hasattr(L, "ebpf_steer"):
+        L.ebpf_rss_hash.argtypes = [ctypes.POINTER(RssDesc), vp]
+        L.ebpf_steer_workspace_bytes.argtypes = [u64, ctypes.c_uint32]
+        L.ebpf_steer_workspace_bytes.restype = u64
+        L.ebpf_steer.argtypes = [vp, u64, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, vp, u64, vp]
     L.ebpf_strerror.argtypes = [ctypes.c_int]
     L.ebpf_strerror.restype = ctypes.c_char_p
     L.ebpf_version.restype = ctypes.c_char_p

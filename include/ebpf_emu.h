@@ -512,6 +512,95 @@ uint64_t ebpf_pcap_gather_workspace_bytes(uint64_t n);
  * aligned; EBPF_ETOOBIG for out_bytes > 4 GiB or n > UINT32_MAX. */
 int ebpf_pcap_gather(const ebpf_pcap_gather_desc* p, ebpf_stream_t stream);
 
+/* ---- RSS flow steering: which receive queue a packet arrives on ----
+ * (new: no reference counterpart.) A NIC fills its RX queues by receive-side scaling: a Toeplitz
+ * hash of the packet's address and port tuple (the Microsoft RSS specification), looked up in an
+ * indirection table. ebpf_rss_hash is that hash for a whole batch, ebpf_steer the stable partition
+ * of the packet numbers by the queue the table gives. Both are asynchronous and ordered on
+ * `stream`, make no host synchronisation and allocate nothing when a workspace is passed. */
+#define EBPF_RSS_IPV4      1u   /* src, dst                      (8 bytes)  */
+#define EBPF_RSS_IPV4_TCP  2u   /* src, dst, sport, dport        (12 bytes) */
+#define EBPF_RSS_IPV4_UDP  4u
+#define EBPF_RSS_IPV6      8u   /* src, dst                      (32 bytes) */
+#define EBPF_RSS_IPV6_TCP 16u   /* src, dst, sport, dport        (36 bytes) */
+#define EBPF_RSS_IPV6_UDP 32u
+typedef struct ebpf_rss_desc {
+  const uint8_t* frames;    /* the batch, as in ebpf_gather_desc: packet i at frames + offsets[i], */
+  const uint32_t* offsets;  /*   or frames + i*stride when NULL; its length lens[i], or stride */
+  const uint16_t* lens;     /*   when NULL (then stride <= 65535). DEVICE pointers, any alignment */
+  uint64_t stride;
+  uint64_t n;               /* packets in the batch (<= UINT32_MAX) */
+  uint8_t key[40];          /* HOST bytes, by value: the RSS key */
+  uint32_t types;           /* the EBPF_RSS_* input types enabled */
+  uint32_t* hash;           /* device u32[n] */
+  uint8_t* type;            /* optional device u8[n]: the one EBPF_RSS_* bit used, 0 = not hashed */
+} ebpf_rss_desc;
+
+/* THE HASH (Toeplitz). The key is a big-endian bit string, key bit 0 the most significant bit of
+ * key[0]. The input is a byte string taken in network order as it lies in the packet, input bit 0
+ * the most significant bit of input byte 0. hash = the XOR, over every set input bit i, of the 32
+ * key bits [i, i + 32) read as a big-endian number. A 36-byte input uses exactly the 40 key bytes.
+ *
+ * THE PARSE. Only the packet's bytes [0, len) are used. be16 = a big-endian 16-bit field.
+ *   L2: the ethertype is be16 at 12; while it is 0x8100 or 0x88A8 (a VLAN tag, 4 bytes) the tag is
+ *     skipped and the ethertype is the be16 4 bytes on, for up to two tags; the L3 header starts at
+ *     o = 14 + 4 * tags. A third tag, or len < o, is NOT HASHED.
+ *   IPv4 (ethertype 0x0800): needs len >= o + 20, a version nibble of 4 and IHL >= 5, else NOT
+ *     HASHED. The L4 ports are used iff the packet is no fragment ((be16 at o + 6) & 0x3FFF == 0),
+ *     the protocol at o + 9 is 6 (TCP) or 17 (UDP), the matching EBPF_RSS_IPV4_TCP / _UDP is
+ *     enabled and len >= o + 4 * IHL + 4; the input is then src | dst | sport | dport (the bytes at
+ *     o + 12 .. o + 20 and at o + 4 * IHL .. + 4) and the type that _TCP / _UDP bit. Otherwise,
+ *     with EBPF_RSS_IPV4 enabled, the input is src | dst and the type EBPF_RSS_IPV4. Otherwise NOT
+ *     HASHED.
+ *   IPv6 (ethertype 0x86DD): needs len >= o + 40 and a version nibble of 6, else NOT HASHED. The
+ *     ports (at o + 40) are used iff the next-header byte at o + 6 is itself 6 or 17, the matching
+ *     EBPF_RSS_IPV6_TCP / _UDP is enabled and len >= o + 44: extension headers are not walked. The
+ *     input is then src | dst | sport | dport (the bytes at o + 8 .. o + 40 and o + 40 .. o + 44).
+ *     Otherwise, with EBPF_RSS_IPV6 enabled, the input is src | dst (type EBPF_RSS_IPV6).
+ *     Otherwise NOT HASHED.
+ *   Every other ethertype is NOT HASHED. NOT HASHED means hash[i] = 0 and type[i] = 0.
+ * No byte at or past packet + len influences the result, and reads of `frames` stay inside the
+ * aligned 16-byte blocks that hold a byte of the packet. Nothing is written but hash[0, n) and
+ * type[0, n). n == 0 is valid and launches nothing. One launch, no scratch. Returns EBPF_EINVAL,
+ * before any device call, for a NULL descriptor or hash, a NULL frames with n > 0, no packet layout
+ * (no offsets, no lens, stride 0), stride > 65535 without lens, types == 0 or a types bit that is
+ * no EBPF_RSS_*; EBPF_ETOOBIG for n > UINT32_MAX. */
+int ebpf_rss_hash(const ebpf_rss_desc* r, ebpf_stream_t stream);
+
+#define EBPF_STEER_MAX_QUEUES 64
+#define EBPF_STEER_MAX_RETA   128
+
+/* Device scratch ebpf_steer needs (8-byte aligned; needs no zeroing). */
+uint64_t ebpf_steer_workspace_bytes(uint64_t n, uint32_t nq);
+
+/* The stable partition of the packet numbers 0..n-1 into nq receive queues:
+ *   queue(i) = reta[key[i] & (reta_len - 1)]
+ * key: device u32[n] at any 4-byte aligned address (ebpf_rss_hash's hash, or any flow key). reta:
+ * the indirection table, HOST u16[reta_len], copied by value; reta_len a power of two in
+ * 1..EBPF_STEER_MAX_RETA, every entry < nq. reta == NULL selects Linux's default table (reta_len
+ * is then ignored): 128 entries, reta[j] = j % nq. nq is 1..EBPF_STEER_MAX_QUEUES.
+ * Once the call is complete on the stream: bounds[k] = {start_k, count_k} (device u32[nq][2]),
+ * start_k = count_0 + ... + count_{k-1}; queue k is index[start_k .. start_k + count_k) (device
+ * u32[n]); inside a queue the packet numbers ascend. The result is deterministic: a flow's packets
+ * (one key) sit in one queue, in arrival order. Exactly n words of index and 2 * nq words of
+ * bounds are written; with n == 0 bounds is all zero and index is untouched.
+ *
+ * THE PAIR LAYOUT IS A CONTRACT. ebpf_gather, ebpf_scatter and ebpf_pcap_gather read a queue as
+ * start = count[0] + ... + count[queue - 1] and m = count[queue]. So
+ *   count = bounds + 2 * k, queue = 1
+ * hands steering queue k to those three calls as they stand (start = bounds[k][0], m =
+ * bounds[k][1]); they read those two words of `count` and no other.
+ *
+ * workspace: device scratch of ebpf_steer_workspace_bytes(n, nq) bytes, one per stream; NULL =>
+ * library-owned per (device, stream), in the buffer ebpf_verdict_queues' scratch lives in. Three
+ * launches (count, bases, write) whose boundaries are the only ordering between workgroups.
+ * Returns EBPF_EINVAL, before any device call, for nq outside 1..64, a reta_len that is no power of
+ * two in 1..128, a table entry >= nq, a NULL bounds, a NULL key or index with n > 0, or a workspace
+ * that is too small or not 8-byte aligned; EBPF_ETOOBIG for n > UINT32_MAX. */
+int ebpf_steer(const uint32_t* key, uint64_t n, uint32_t nq, const uint16_t* reta,
+               uint32_t reta_len, uint32_t* index, uint32_t* bounds, void* workspace,
+               uint64_t workspace_bytes, ebpf_stream_t stream);
+
 /* Human-readable message for an EBPF_E* code. */
 const char* ebpf_strerror(int err);
 
