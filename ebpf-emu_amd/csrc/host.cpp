@@ -2643,6 +2643,40 @@ int ebpf_steer(const uint32_t* key, uint64_t n, uint32_t nq, const uint16_t* ret
   return launch_steer(a, s) == hipSuccess ? EBPF_OK : EBPF_EHIP;
 }
 
+// ---- checksum offload (csum.hip) ----
+static int csum_call(const ebpf_csum_desc* c, bool fill, ebpf_stream_t stream) {
+  static_assert(kCsWhat == (EBPF_CSUM_IPV4_HDR | EBPF_CSUM_TCP | EBPF_CSUM_UDP),
+                "include/ebpf_emu.h names the checksums");
+  if (!c || (!fill && !c->status)) return EBPF_EINVAL;
+  if (c->n && !c->frames) return EBPF_EINVAL;
+  if (!c->offsets && c->stride == 0 && !c->lens) return EBPF_EINVAL;  // no packet layout
+  if (!c->lens && c->stride > 0xFFFF) return EBPF_EINVAL;
+  if (c->what == 0 || (c->what & ~kCsWhat)) return EBPF_EINVAL;
+  if (c->queue_mask >> EBPF_NQUEUES) return EBPF_EINVAL;
+  if (c->n > 0xFFFFFFFFull) return EBPF_ETOOBIG;
+  if (c->n == 0) return EBPF_OK;  // nothing is launched
+  CsumArgs a{};
+  a.frames = c->frames;
+  a.offsets = c->offsets;
+  a.lens = c->lens;
+  a.stride = c->stride;
+  a.n = c->n;
+  a.what = c->what;
+  a.verdict = c->verdict;
+  a.queue_mask = c->queue_mask;
+  a.status = c->status;
+  hipStream_t s = (hipStream_t)stream;
+  int device = 0;
+  int rc = stream_device(s, &device);
+  if (rc) return rc;
+  DeviceScope on(device);
+  return launch_csum(a, fill, s) == hipSuccess ? EBPF_OK : EBPF_EHIP;
+}
+
+int ebpf_csum_verify(const ebpf_csum_desc* c, ebpf_stream_t stream) { return csum_call(c, false, stream); }
+
+int ebpf_csum_fill(const ebpf_csum_desc* c, ebpf_stream_t stream) { return csum_call(c, true, stream); }
+
 const char* ebpf_strerror(int err) {
   switch (err) {
     case EBPF_OK: return "ok";

@@ -344,4 +344,25 @@ struct SteerArgs {  // ebpf_steer's arguments, checked
 // Three kernels on `stream` (include/ebpf_emu.h ebpf_steer); n >= 1.
 hipError_t launch_steer(const SteerArgs& s, hipStream_t stream);
 
+// ---- checksum offload (csum.hip) ----
+// One wave per workgroup: the LDS arrays are a wave's own, so the two barriers of a pass couple no
+// wave to another one's longer block list.
+constexpr int kCsBlock = 64;              // one lane per packet to parse
+constexpr int kCsWaves = kCsBlock / kWave;
+constexpr int kCsMaxWgs = 8192;           // grid cap (a larger batch: several passes)
+constexpr uint32_t kCsWhat = 7;           // every EBPF_CSUM_IPV4_HDR / _TCP / _UDP bit
+
+struct CsumArgs {  // ebpf_csum_desc, checked
+  uint8_t* frames;
+  const uint32_t* offsets;
+  const uint16_t* lens;
+  uint64_t stride, n;
+  uint32_t what;
+  uint32_t queue_mask;     // the caller's; not looked at when verdict == nullptr
+  const uint8_t* verdict;  // optional
+  uint8_t* status;         // optional (fill)
+};
+// One kernel on `stream` (include/ebpf_emu.h ebpf_csum_verify / ebpf_csum_fill); n >= 1.
+hipError_t launch_csum(const CsumArgs& c, bool fill, hipStream_t stream);
+
 }  // namespace ebpfemu

@@ -25,6 +25,10 @@ def __getattr__(name):  # lazy: these import torch
         from . import rss
 
         return getattr(rss, name)
+    if name in ("csum_verify", "csum_fill"):
+        from . import csum
+
+        return getattr(csum, name)
     if name in ("Emu", "EmuPanic"):
         from . import emu
 

@@ -56,6 +56,7 @@ EXPORTS = ["ebpf_batch_init", "ebpf_prog_load", "ebpf_prog_load_hex", "ebpf_prog
            "ebpf_gather", "ebpf_scatter_workspace_bytes", "ebpf_scatter",
            "ebpf_pcap_gather_workspace_bytes", "ebpf_pcap_gather",
            "ebpf_rss_hash", "ebpf_steer_workspace_bytes", "ebpf_steer",
+           "ebpf_csum_verify", "ebpf_csum_fill",
            "ebpf_strerror", "ebpf_version"]
 
 
@@ -127,6 +128,19 @@ class RssDesc(ctypes.Structure):  # ebpf_rss_desc
                 ("lens", ctypes.c_void_p), ("stride", ctypes.c_uint64), ("n", ctypes.c_uint64),
                 ("key", ctypes.c_uint8 * 40), ("types", ctypes.c_uint32),
                 ("hash", ctypes.c_void_p), ("type", ctypes.c_void_p)]
+
+
+# ebpf_csum_desc.what (EBPF_CSUM_*) and the status byte's bits
+CSUM_IPV4_HDR, CSUM_TCP, CSUM_UDP = 1, 2, 4
+CSUM_ALL = 7
+CSUM_L3_GOOD, CSUM_L3_BAD, CSUM_L4_GOOD, CSUM_L4_BAD, CSUM_L4_NONE = 1, 2, 4, 8, 16
+
+
+class CsumDesc(ctypes.Structure):  # ebpf_csum_desc
+    _fields_ = [("frames", ctypes.c_void_p), ("offsets", ctypes.c_void_p),
+                ("lens", ctypes.c_void_p), ("stride", ctypes.c_uint64), ("n", ctypes.c_uint64),
+                ("what", ctypes.c_uint32), ("verdict", ctypes.c_void_p),
+                ("queue_mask", ctypes.c_uint32), ("status", ctypes.c_void_p)]
 
 
 class EbpfError(RuntimeError):
@@ -215,6 +229,10 @@ def lib():
         L.ebpf_steer_workspace_bytes.argtypes = [u64, ctypes.c_uint32]
         L.ebpf_steer_workspace_bytes.restype = u64
         L.ebpf_steer.argtypes = [vp, u64, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, vp, u64, vp]
+    # (and one from before the checksum offload)
+    if hasattr(L, "ebpf_csum_verify"):
+        L.ebpf_csum_verify.argtypes = [ctypes.POINTER(CsumDesc), vp]
+        L.ebpf_csum_fill.argtypes = [ctypes.POINTER(CsumDesc), vp]
     L.ebpf_strerror.argtypes = [ctypes.c_int]
     L.ebpf_strerror.restype = ctypes.c_char_p
     L.ebpf_version.restype = ctypes.c_char_p

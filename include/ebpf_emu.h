@@ -601,6 +601,87 @@ int ebpf_steer(const uint32_t* key, uint64_t n, uint32_t nq, const uint16_t* ret
                uint32_t reta_len, uint32_t* index, uint32_t* bounds, void* workspace,
                uint64_t workspace_bytes, ebpf_stream_t stream);
 
+/* ---- Checksum offload: the Internet checksum of a whole batch ----
+ * (new: no reference counterpart.) A NIC's RX descriptor says whether the IPv4 header checksum and
+ * the TCP / UDP checksum of a packet were good, and its TX side writes them into packets that a
+ * program rewrote. ebpf_csum_verify is the first for a whole batch, ebpf_csum_fill the second. Both
+ * are asynchronous and ordered on `stream`, make no host synchronisation, need no scratch and
+ * allocate nothing; each is one launch. */
+#define EBPF_CSUM_IPV4_HDR 1u   /* the IPv4 header checksum */
+#define EBPF_CSUM_TCP      2u   /* TCP over IPv4 and IPv6 */
+#define EBPF_CSUM_UDP      4u   /* UDP over IPv4 and IPv6 */
+/* status byte */
+#define EBPF_CSUM_L3_GOOD  1u   /* fill: the header field was written */
+#define EBPF_CSUM_L3_BAD   2u
+#define EBPF_CSUM_L4_GOOD  4u   /* fill: the L4 field was written */
+#define EBPF_CSUM_L4_BAD   8u
+#define EBPF_CSUM_L4_NONE 16u   /* verify only: UDP over IPv4 whose checksum field is 0 (none sent) */
+typedef struct ebpf_csum_desc {
+  uint8_t* frames;          /* the batch, as in ebpf_rss_desc: packet i at frames + offsets[i], or */
+  const uint32_t* offsets;  /*   frames + i*stride when NULL; its length lens[i], or stride when */
+  const uint16_t* lens;     /*   NULL (then stride <= 65535). DEVICE pointers, any alignment. */
+  uint64_t stride;          /*   ebpf_csum_verify only reads frames, ebpf_csum_fill WRITES it */
+  uint64_t n;               /* packets in the batch (<= UINT32_MAX) */
+  uint32_t what;            /* EBPF_CSUM_IPV4_HDR | _TCP | _UDP, non-zero */
+  const uint8_t* verdict;   /* optional device u8[n]: selects packets by queue class */
+  uint32_t queue_mask;      /* bit q set: packets of ebpf_verdict_queues' class q are processed (q =
+                               v < 5 ? v : v == 0xFF ? 6 : 5); not applied when verdict == NULL */
+  uint8_t* status;          /* optional device u8[n] (any alignment), OVERWRITTEN for all n */
+} ebpf_csum_desc;
+
+/* TERMS. be16 = a big-endian 16-bit field. fold(t): while (t >> 16) t = (t & 0xFFFF) + (t >> 16).
+ * sum16(bytes) = the plain integer sum of the be16 words of a byte string, an odd last byte counting
+ * as the high byte of a word whose low byte is 0. Only the packet's bytes [0, len) are used.
+ *
+ * SELECTION. With a verdict array, packet i is processed iff bit q(verdict[i]) of queue_mask is
+ * set. A packet that is not selected gets status 0 and is not touched.
+ *
+ * THE PARSE.
+ *   L2: exactly ebpf_rss_hash's: up to two VLAN tags are skipped, the L3 header starts at o = 14 +
+ *     4 * tags; a third tag, len < o, or any ethertype but the two below gives status 0.
+ *   IPv4 (ethertype 0x0800): needs len >= o + 20, a version nibble of 4, IHL >= 5 and len >= o + H,
+ *     H = 4 * IHL; else status 0.
+ *     L3 (with EBPF_CSUM_IPV4_HDR): GOOD iff fold(sum16(bytes [o, o + H))) == 0xFFFF, else BAD.
+ *     L4: with T = be16 at o + 2 and p = o + H it needs ALL of: T >= H; o + T <= len (the packet
+ *     holds the whole datagram; bytes past o + T are padding and ignored); no fragment ((be16 at
+ *     o + 6) & 0x3FFF == 0); and, with L = T - H, either protocol (the byte at o + 9) 6 with
+ *     EBPF_CSUM_TCP and L >= 20, or protocol 17 with EBPF_CSUM_UDP, L >= 8 and be16 at p + 4 == L.
+ *     Otherwise no L4 bit is set. The sum is
+ *       C = fold(sum16(src | dst) + protocol + L + sum16(bytes [p, p + L)))
+ *     (src | dst the 8 bytes at o + 12), the checksum field at p + 16 for TCP and p + 6 for UDP.
+ *   IPv6 (ethertype 0x86DD): needs len >= o + 40 and a version nibble of 6, else status 0. There is
+ *     no L3 bit. L4 needs ALL of: the next-header byte at o + 6 is itself 6 or 17 and enabled
+ *     (extension headers are not walked); with P = be16 at o + 4, p = o + 40 and L = P: p + L <=
+ *     len; the same minimums on L and the same UDP length equality. The sum is
+ *       C = fold(sum16(src | dst) + next header + L + sum16(bytes [p, p + L)))
+ *     (src | dst the 32 bytes at o + 8).
+ *
+ * VERIFY. UDP over IPv4 whose two field bytes are 0 gets EBPF_CSUM_L4_NONE, and nothing is summed.
+ * Otherwise EBPF_CSUM_L4_GOOD iff C == 0xFFFF, else EBPF_CSUM_L4_BAD. The definition is purely
+ * arithmetic: a UDP over IPv6 field of 0 is summed like any other value. frames is only read.
+ *
+ * FILL. The field's two bytes count as 0 in the sum; the value is ~C & 0xFFFF, for UDP a value of
+ * 0 becomes 0xFFFF; it is written big-endian at the field. The IPv4 header field at o + 10 is
+ * filled by the same rule (over the header's sum), without the 0xFFFF substitution. status gets
+ * EBPF_CSUM_L3_GOOD / _L4_GOOD for each field written, never _BAD or _NONE. Fill writes those
+ * two-byte fields and NO other byte of frames: not the rest of the packet, not a neighbour that
+ * abuts at any alignment, and no wider word is read-modify-written (the fields are stored byte by
+ * byte).
+ *
+ * READS of frames stay inside the aligned 16-byte blocks that hold a byte of the packet, and no
+ * byte at or past packet + len influences any result. Packets must not overlap (not checked).
+ * Nothing else is written but status[0, n). n == 0 is valid and launches nothing.
+ *
+ * OUT OF SCOPE: ICMP and ICMPv6, IPv6 extension headers, SCTP, tunnelled inner headers, jumbograms
+ * (an IPv6 payload length of 0 is taken as L = 0), partial (CHECKSUM_PARTIAL-style) sums.
+ *
+ * Both return EBPF_EINVAL, before any device call, for a NULL descriptor, a NULL frames with n > 0,
+ * no packet layout (no offsets, no lens, stride 0), stride > 65535 without lens, what == 0 or a
+ * what bit that is no EBPF_CSUM_*, a queue_mask bit at or above 1 << EBPF_NQUEUES (with or without
+ * a verdict array); ebpf_csum_verify also for a NULL status. EBPF_ETOOBIG for n > UINT32_MAX. */
+int ebpf_csum_verify(const ebpf_csum_desc* c, ebpf_stream_t stream);
+int ebpf_csum_fill(const ebpf_csum_desc* c, ebpf_stream_t stream);
+
 /* Human-readable message for an EBPF_E* code. */
 const char* ebpf_strerror(int err);
 
